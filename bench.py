@@ -9,7 +9,12 @@ synthetic episodes, NCHW fp32, all 19 views) are in HBM before the timed region;
 fresh numpy permutations.  One process per GPU; episodes shard across ranks with no data-path
 collective (only a final all-gather of per-episode accuracies), so scaling is "weak".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes-per-batch E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes-per-batch E] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, config).  Everything else the
+benchmark measures or checks -- rooflines and per-launch timings, power, accuracy and the validation against golden G9, the
+CPU baseline, the fixed-job strong-scaling leg and the `other_configs` children -- runs only with --full.  --dump-outputs DIR
+writes what the last timed step returned to its caller as DIR/<name>.npy (rank 0's share at N > 1).
 """
 import argparse
 import json
@@ -131,6 +136,24 @@ def g9_episodes(n, dev, gen_examples=17, workers=None):
         return [v.to(dev) for v in synthetic.test_episode(G9_EP_SEED0 + i, 5, 5, 15, 84, gen_examples=gen_examples, noise=G9_NOISE)]
     with ThreadPoolExecutor(max_workers=workers or min(8, host_threads())) as ex:
         return list(ex.map(make, range(n)))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as ``out_dir/<name>.npy`` (float32, or float64 where the path returned float64); at most 64 MB
+    in all, so that two builds can be compared output for output."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class PowerSampler:
@@ -431,7 +454,7 @@ def other_configs_children(args):
     import subprocess
     out = {}
     for key, what, extra, tmo in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-standalone", "--strong-episodes", "0",
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-standalone", "--strong-episodes", "0",
                                                                      "--validate-episodes", "0", "--no-other-configs"]
         t0 = time.perf_counter()
         try:
@@ -445,7 +468,7 @@ def other_configs_children(args):
             out[key] = {"what": what, "error": "child failed rc=%d: %s" % (r.returncode, r.stderr[-300:])}
             continue
         j = json.loads(line[-1])
-        rec = {"what": what, "command": "python bench.py " + " ".join(extra), "value": j["value"], "unit": j["unit"],
+        rec = {"what": what, "command": "python bench.py --full " + " ".join(extra), "value": j["value"], "unit": j["unit"],
                "ms_per_step": j["ms_per_step"], "steps": j["steps"], "episodes_per_step": j["config"].get("episodes_per_step", 1),
                "process_wall_s": round(wall, 1)}
         roofs = {k: j[k] for k in ("roofline", "roofline_mfma", "roofline_mfma_x3") if j.get(k)}
@@ -649,9 +672,13 @@ def bench_metatrain(args, rank, world, dev, dist):
         t = torch.tensor([dt], device="cpu" if dist.get_backend() == "gloo" else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    census = rank_census(dist, dev)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the step receives: the loss of the last timed step and the parameters it left behind
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1),
+                                         "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
+    census = rank_census(dist, dev) if args.full else None
     roof = cpu = None
-    if rank == 0 and not finetune:
+    if rank == 0 and not finetune and args.full:
         roof = metatrain_roofline(model, opt, eps, dt / args.steps, loss_fn, kk)
         if not args.no_cpu_baseline:
             cpu = cpu_baseline_subprocess(args.gen_examples, workload="metatrain")
@@ -671,7 +698,7 @@ def bench_metatrain(args, rank, world, dev, dist):
                                           if args.train_source == "pool" else "eight pre-made fp32 episodes, cycled"),
                        "parallelism": "episode-parallel x%d" % world},
             "last_loss": round(float(loss.detach().cpu()), 4), "graphed": graphed is not None and graphed.graph is not None,
-            "rccl_ranks": census, "roofline": roof, "cpu_baseline": cpu}))
+            **({"rccl_ranks": census, "roofline": roof, "cpu_baseline": cpu} if args.full else {})}))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -709,7 +736,7 @@ def main():
                     "(RandomResizedCrop + ImageJitter + flip) instead of Resize + CenterCrop")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default line only: skip the short child runs of BASELINE configs[2] / [3] / [4] and of 224x224 (`other_configs`)")
+                    help="with --full: skip the short child runs of BASELINE configs[2] / [3] / [4] and of 224x224 (`other_configs`)")
     ap.add_argument("--no-standalone", action="store_true", help="skip the extra standalone launches of the dominant kernel "
                     "(roofline.standalone); used for the PMC passes so that per-launch counter means cover the step mix only")
     ap.add_argument("--cpu-baseline-only", action="store_true",
@@ -729,8 +756,16 @@ def main():
                     help="self-validation: the first V slots of the resident pool are the first V episodes of the accuracy golden "
                          "G9 (tests/golden/g9_accuracy.npz, the reference's own finetune() at this configuration); before the "
                          "warm-up one batch is run on the golden's numpy permutation stream and its per-episode accuracies are "
-                         "compared with the reference's (0 = off)")
+                         "compared with the reference's (0 = off; --full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: rooflines and per-launch timings, power, accuracy, the "
+                         "validation against golden G9, the CPU baseline, the fixed-job strong-scaling leg and the other_configs children")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (scores of every episode of the batch; "
+                         "metatrain: loss and parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.episodes_per_batch is None:
         args.episodes_per_batch = int(os.environ.get("MFT_EPB", {20: 96, 50: 64}.get(args.n_shot, 128)))
 
@@ -755,10 +790,10 @@ def main():
         # (python -m torch.distributed.run, one rank per GPU over RCCL), relays their output -- rank 0 prints the ONE JSON
         # line -- and exits with their status
         raise SystemExit(self_launch(args.gpus))
-    if (args.gpus == 1 and "RANK" not in os.environ and not args.no_other_configs and not args.strong_only
+    if (args.full and args.gpus == 1 and "RANK" not in os.environ and not args.no_other_configs and not args.strong_only
             and args.workload == "finetune" and args.strong_episodes > 0 and args.n_shot == 5 and args.image_size == 84 and args.epochs == 5
             and args.gen_examples == 17 and not args.device_aug):
-        # the default line: this process never touches the GPU.  It runs the headline measurement as a child (the whole path below,
+        # the --full line: this process never touches the GPU.  It runs the headline measurement as a child (the whole path below,
         # with --no-other-configs), THEN the short children of the other BASELINE configurations -- each alone on the GPU, none
         # before the headline (run first they cost it 7 %: 82.7 instead of 89.7 episodes/s, measured, through the package's thermal
         # state; run beside a parent that still holds its engine the 50-shot child does not get its stem caches) -- and prints the
@@ -770,7 +805,7 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d was started with WORLD_SIZE=%d" % (args.gpus, world))
     strong = others = None
-    if (not args.strong_only and args.workload == "finetune" and args.strong_episodes > 0 and args.n_shot == 5 and args.image_size == 84
+    if (args.full and not args.strong_only and args.workload == "finetune" and args.strong_episodes > 0 and args.n_shot == 5 and args.image_size == 84
             and args.epochs == 5 and args.gen_examples == 17 and not args.device_aug):
         strong = strong_scaling_child(args, rank, world)          # before this process initialises the GPU
     if not torch.cuda.is_available():
@@ -828,7 +863,7 @@ def main():
         args.no_cpu_baseline = True
     views = 2 + args.gen_examples
     # G9's weights (seeded backbone + head meta-trained with the reference): accuracies are then comparable with the golden
-    validate = (args.validate_episodes if (n_shot == 5 and size == 84 and args.epochs == 5 and args.gen_examples == 17
+    validate = (args.validate_episodes if (args.full and n_shot == 5 and size == 84 and args.epochs == 5 and args.gen_examples == 17
                                             and not args.device_aug and rank == 0) else 0)
     validate = min(validate, E)
     state = g9_state() if (n_shot == 5) else synthetic.gnnnet_state_dict(seed=0)
@@ -910,13 +945,14 @@ def main():
     for _ in range(args.warmup):
         one_batch()
     sync_all()
-    power = PowerSampler() if rank == 0 else None
+    power = PowerSampler() if (rank == 0 and args.full) else None
     if power is not None:
         power.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         sc = one_batch()
-        accs.append(sc)
+        if args.full:
+            accs.append(sc)
     sync_all()
     dt = time.perf_counter() - t0
     power = power.stop() if power is not None else None
@@ -925,18 +961,21 @@ def main():
         t = torch.tensor([dt], device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    acc = torch.cat(accs).argmax(2).cpu().numpy() == y_query[None]
-    acc_ep = acc.mean(1) * 100.0
-    if dist is not None:
-        gathered = [torch.zeros(len(acc_ep), device=cdev, dtype=torch.float64) for _ in range(world)]
-        dist.all_gather(gathered, torch.tensor(acc_ep, device=cdev, dtype=torch.float64))
-        acc_ep = torch.cat(gathered).cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": sc})          # (E, n_way * n_query, n_way): what run_batch returned last
+    if args.full:
+        acc = torch.cat(accs).argmax(2).cpu().numpy() == y_query[None]
+        acc_ep = acc.mean(1) * 100.0
+        if dist is not None:
+            gathered = [torch.zeros(len(acc_ep), device=cdev, dtype=torch.float64) for _ in range(world)]
+            dist.all_gather(gathered, torch.tensor(acc_ep, device=cdev, dtype=torch.float64))
+            acc_ep = torch.cat(gathered).cpu().numpy()
 
     # ---- rooflines: one more identical batch (same two-stream pipeline) with an event pair around every launch of the
     # two kernel families.  In-situ durations include the slowdown from the kernel co-running on the other stream; the
     # rocprofv3 kernel-trace of this same command (profiles/) must and does show the same averages.
     roof = roof_mfma = roof_x3 = None
-    if rank == 0:
+    if rank == 0 and args.full:
         fam = timed_launches(one_batch)
         adam_events, conv_events, x3_events = fam["adam"], fam["f32"], fam["x3"]
         a_ms = sum(t for t, _ in adam_events)
@@ -1091,7 +1130,7 @@ def main():
                      "algorithmic_gflop_per_launch": round(tot_fl / n_launch / 1e9, 3)}
 
     placement = e.adapt.placement
-    census = rank_census(dist, dev)
+    census = rank_census(dist, dev) if args.full else None
 
     if rank == 0:
         total_eps = E * args.steps * world
@@ -1123,10 +1162,6 @@ def main():
             "episode_tflop": round(fl / 1e12, 4),
             "whole_path_tflops": round(value * fl / 1e12, 2),
             "whole_path_frac_of_f32_mfma_peak": round(value * fl / world / PEAK_F32_MFMA, 4),
-            "mean_acc": round(float(acc_ep.mean()), 2),
-            "mean_acc_note": "all timed batches, resident pool re-run with fresh permutations each batch; weights = golden G9's "
-                             "(meta-trained head), so this is a real accuracy, not chance" if n_shot == 5 else "seed-0 random head",
-            "validation": validation,
             # whole path against the same HBM roof: the adaptable-state bytes an episode moves (per inner step: forward weights
             # 14.7 MB + data-gradient re-read 9.4 MB + Adam read/write of w, m, v 88.2 MB) over the wall time of
             # the timed region, everything else (trunk, final pass, ingest, host) counted as zero bytes
@@ -1136,20 +1171,27 @@ def main():
                                "achieved": round(value / world * gb_step * n_steps_ep, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                "frac": round(value / world * gb_step * n_steps_ep / PEAK_HBM_GBS, 4),
                                "fused_next_forward": bool(e.fused_last_loop), "fused_next_forward_policy": bool(e.fuse_next)},
-            "power": power if power is None else dict(power, joules_per_episode=round(power["socket_w_median"] * dt / (E * args.steps), 2)),
             "slab_placement": placement,
-            "strong_scaling": strong,
-            "rccl_ranks": census,
-            "roofline": roof,
-            "roofline_mfma": roof_mfma,
-            "roofline_mfma_x3": roof_x3,
-            # in-situ launch time of one batch by kernel family (ms, HIP events on each launcher's own stream; the two queues overlap,
-            # so the sum exceeds the wall): which family a configuration is bound by
-            "launch_time_share": {k: round(v, 2) for k, v in share_ms.items()},
-            "other_configs": others,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline_subprocess(args.gen_examples)
+        if args.full:
+            out.update({
+                "mean_acc": round(float(acc_ep.mean()), 2),
+                "mean_acc_note": "all timed batches, resident pool re-run with fresh permutations each batch; weights = golden G9's "
+                                 "(meta-trained head), so this is a real accuracy, not chance" if n_shot == 5 else "seed-0 random head",
+                "validation": validation,
+                "power": power if power is None else dict(power, joules_per_episode=round(power["socket_w_median"] * dt / (E * args.steps), 2)),
+                "strong_scaling": strong,
+                "rccl_ranks": census,
+                "roofline": roof,
+                "roofline_mfma": roof_mfma,
+                "roofline_mfma_x3": roof_x3,
+                # in-situ launch time of one batch by kernel family (ms, HIP events on each launcher's own stream; the two queues overlap,
+                # so the sum exceeds the wall): which family a configuration is bound by
+                "launch_time_share": {k: round(v, 2) for k, v in share_ms.items()},
+                "other_configs": others,
+            })
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline_subprocess(args.gen_examples)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

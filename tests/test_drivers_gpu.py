@@ -387,7 +387,7 @@ def test_bench_two_ranks_one_json_line(workload, launcher):
     else:
         cmd = [sys.executable] + tail
     if workload == "finetune":
-        cmd += ["--episodes-per-batch", "8", "--epochs", "1", "--gen-examples", "2", "--no-standalone", "--no-cpu-baseline"]
+        cmd += ["--full", "--episodes-per-batch", "8", "--epochs", "1", "--gen-examples", "2", "--no-standalone", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -414,7 +414,7 @@ def test_bench_collectives_on_rccl_with_one_rank(workload):
                WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     for k in ("MFT_BENCH_ONE_DEVICE", "MFT_DIST_BACKEND", "MFT_ONE_DEVICE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", workload]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", workload, "--full"]
     if workload == "finetune":
         cmd += ["--episodes-per-batch", "8", "--epochs", "1", "--gen-examples", "2", "--no-standalone", "--no-cpu-baseline", "--strong-episodes", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
@@ -423,6 +423,42 @@ def test_bench_collectives_on_rccl_with_one_rank(workload):
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["unit"] == "episodes/s"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["finetune", "metatrain"])
+def test_bench_plain_run_dumps_outputs(tmp_path, workload):
+    """A plain `bench.py` (no --full) times exactly --steps steps, prints the headline fields without the extra measurements, and
+    with --dump-outputs writes what the last timed step returned; the same arguments give the same inputs, so a second run
+    writes the same arrays."""
+    import json
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
+    for k in ("WORLD_SIZE", "RANK", "MFT_BENCH_ONE_DEVICE", "MFT_DIST_BACKEND", "MFT_FORCE_COLLECTIVES"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload]
+    if workload == "finetune":
+        cmd += ["--episodes-per-batch", "8", "--epochs", "1", "--gen-examples", "2"]
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        assert d["unit"] == "episodes/s" and d["higher_is_better"] is True
+        for k in ("roofline", "cpu_baseline", "strong_scaling", "other_configs", "validation", "rccl_ranks"):
+            assert k not in d, k
+        dumps.append({f[:-4]: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))})
+    a, b = dumps
+    if workload == "finetune":
+        assert sorted(a) == ["scores"] and a["scores"].shape == (8, 75, 5) and a["scores"].dtype == np.float32
+        assert np.allclose(a["scores"].sum(2), 1.0, atol=1e-4)                 # softmax scores of every query
+    else:
+        assert sorted(a) == ["loss", "params"] and a["params"].dtype == np.float32 and a["params"].size > 5e6
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert np.isfinite(a[k]).all() and np.allclose(a[k], b[k], rtol=1e-3, atol=1e-4), k
 
 
 def test_bench_self_launch_propagates_failure():

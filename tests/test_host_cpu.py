@@ -129,33 +129,35 @@ def test_step_tables_shapes():
     assert np.array_equal(lab[:5], e.y_support[perms[0][1][5:10]])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout only exists in the build container")
 def test_checkpoints_interchange_with_the_reference(tmp_path):
     """a checkpoint written by this package ({'epoch','state'} .tar, train.py:46-48) loads strictly
     into the REFERENCE's own GnnNet(ResNet10) and a reference-written one loads strictly here, including the extra
-    feature2./feature3. copies a meta-fine-tuned reference model carries (train.py:197-202 drops them)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import make_golden as MG
-    mods = MG.import_reference()
-    ref_gnnnet, ref_backbone = mods["methods.gnnnet"], mods["backbone"]
+    feature2./feature3. copies a meta-fine-tuned reference model carries (train.py:197-202 drops them).  The reference's side
+    is its state_dict schema -- key order, shapes, dtypes -- recorded in golden G20 (oracle/make_golden_g20.py): a strict load
+    needs exactly these keys with exactly these shapes."""
+    g20 = np.load(os.path.join(ROOT, "tests", "golden", "g20_reference_state_dict.npz"))
+    ref = [(str(k), tuple(int(d) for d in s_[:n]), str(t)) for k, s_, n, t in zip(g20["keys"], g20["shapes"], g20["ndim"], g20["dtypes"])]
+    assert len(ref) == 140
     ours = gnnnet.GnnNet(backbone.ResNet10, n_way=5, n_support=5)
     ours.load_state_dict(synthetic.gnnnet_state_dict(seed=3))
     f = str(tmp_path / "399.tar")
     torch.save({"epoch": 399, "state": ours.state_dict()}, f)
-    ref = ref_gnnnet.GnnNet(MG.make_factory(ref_backbone, 84), n_way=5, n_support=5)
-    ref.load_state_dict(torch.load(f)["state"], strict=True)
-    for k, v in ref.state_dict().items():
+    loaded = torch.load(f)["state"]
+    assert [(k, tuple(v.shape), str(v.dtype).replace("torch.", "")) for k, v in loaded.items()] == ref
+    for k, v in loaded.items():
         assert torch.equal(v, ours.state_dict()[k]), k
     # the other direction, with the meta-fine-tuning copies present
-    sd = ref.state_dict()
-    sd.update({k.replace("feature.", "feature2.", 1): v for k, v in ref.state_dict().items() if k.startswith("feature.")})
+    gen = torch.Generator().manual_seed(5)
+    sd = {k: (torch.randn(s_, generator=gen) if t == "float32" else torch.zeros(s_, dtype=getattr(torch, t))) for k, s_, t in ref}
+    sd.update({k.replace("feature.", "feature2.", 1): v.clone() for k, v in sd.items() if k.startswith("feature.")})
     g = str(tmp_path / "600.tar")
     torch.save({"epoch": 600, "state": sd}, g)
     state = {k: v for k, v in torch.load(g)["state"].items() if "feature2." not in k and "feature3." not in k}
     ours2 = gnnnet.GnnNet(backbone.ResNet10, n_way=5, n_support=5)
     ours2.load_state_dict(state, strict=True)
-    assert list(ours2.state_dict().keys()) == list(ref.state_dict().keys())
+    assert list(ours2.state_dict().keys()) == [k for k, _, _ in ref]
+    for k, v in ours2.state_dict().items():
+        assert torch.equal(v, sd[k]), k
 
 
 def test_engine_cache_is_content_keyed():
@@ -292,6 +294,25 @@ def test_bench_helpers_and_pmc_provenance(tmp_path, monkeypatch):
     empty.cards = []
     empty.start()
     assert empty.stop() is None
+
+
+def test_bench_dump_outputs_and_arguments(tmp_path):
+    """bench.dump_outputs writes float32 (float64 stays float64) DIR/<name>.npy files and refuses more than 64 MB in all; --steps
+    below 1 is refused before anything runs."""
+    import subprocess
+    import sys
+    import bench
+    bench.dump_outputs(str(tmp_path / "d"), {"scores": torch.ones(2, 3, dtype=torch.float16), "loss": np.array([0.5]),
+                                             "params": torch.arange(4, dtype=torch.float32)})
+    got = {f: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(str(tmp_path / "d")))}
+    assert sorted(got) == ["loss.npy", "params.npy", "scores.npy"]
+    assert got["scores.npy"].dtype == np.float32 and got["scores.npy"].shape == (2, 3) and got["loss.npy"].dtype == np.float64
+    assert np.array_equal(got["params.npy"], np.arange(4, dtype=np.float32))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
+    r = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
 
 
 def test_slab_placement_choice():

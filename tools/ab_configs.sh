@@ -5,7 +5,7 @@ mkdir -p $(dirname $OUT); : > $OUT
 COMMON="--no-cpu-baseline --strong-episodes 0 --no-standalone --validate-episodes 0"
 for args in "--n-shot 20 --episodes-per-batch 96 --steps 2 --warmup 1" "--n-shot 50 --episodes-per-batch 128 --steps 1 --warmup 1" "--image-size 224 --episodes-per-batch 32 --steps 2 --warmup 1" "--episodes-per-batch 120 --steps 4 --warmup 1" "--episodes-per-batch 32 --steps 8 --warmup 2"; do
   for v in $A $B; do
-    env $VAR=$v python3 bench.py $args $COMMON 2>/dev/null | tail -1 > /tmp/ab_line.json
+    env $VAR=$v python3 bench.py --full $args $COMMON 2>/dev/null | tail -1 > /tmp/ab_line.json
     python3 - "$VAR=$v $args" >> $OUT <<'PY'
 import json, sys
 try:

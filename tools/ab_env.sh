@@ -6,7 +6,7 @@ mkdir -p $(dirname $OUT)
 : > $OUT
 for i in $(seq 1 $N); do
   for v in $A $B; do
-    env $VAR=$v python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --strong-episodes 0 2>/dev/null | tail -1 > /tmp/ab_line.json
+    env $VAR=$v python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --strong-episodes 0 2>/dev/null | tail -1 > /tmp/ab_line.json
     python3 - "$VAR=$v" >> $OUT <<'PY'
 import json, sys
 d = json.load(open('/tmp/ab_line.json'))

@@ -6,7 +6,7 @@ mkdir -p $(dirname $OUT); : > $OUT
 for i in 1 2; do
   for cfg in "$@"; do
     if [ "$cfg" = "-" ]; then envs=""; else envs="$cfg"; fi
-    env $envs python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --strong-episodes 0 --no-standalone 2>/dev/null | tail -1 > /tmp/ab_line.json
+    env $envs python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --strong-episodes 0 --no-standalone 2>/dev/null | tail -1 > /tmp/ab_line.json
     python3 - "$cfg" >> $OUT <<'PY'
 import json, sys
 try:

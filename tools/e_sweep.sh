@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/e_sweep; mkdir -p $O
 for E in ${1:-128 160 192 256}; do
-  python bench.py --episodes-per-batch $E --steps ${2:-4} --warmup 1 --no-cpu-baseline --no-standalone --strong-episodes 0 --validate-episodes 0 > $O/E$E.json 2> $O/E$E.err
+  python bench.py --full --episodes-per-batch $E --steps ${2:-4} --warmup 1 --no-cpu-baseline --no-standalone --strong-episodes 0 --validate-episodes 0 > $O/E$E.json 2> $O/E$E.err
   python - $O/E$E.json $E <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

@@ -8,15 +8,15 @@ HEAD=${3:-unknown}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/final
 mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-standalone --validate-episodes 0 --strong-episodes 0 > $O/kt_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-standalone --validate-episodes 0 --strong-episodes 0 > $O/kt_bench.log 2>&1
 tail -1 $O/kt_bench.log | cut -c1-300
 python3 tools/rocpd_stats.py $(find $O/kt -name "*.db" | head -1) > $O/${TAG}_kernel_stats_E128_pipelined.txt
 head -8 $O/${TAG}_kernel_stats_E128_pipelined.txt | cut -c1-180
 find $O/kt -name "*.db" -delete
 PMCARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-standalone --epochs 1 --gen-examples 2 --no-pipeline --no-defer-final --validate-episodes 0"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py $PMCARGS > $O/pmc_f.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py $PMCARGS > $O/pmc_w.log 2>&1
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_m -- python3 bench.py $PMCARGS > $O/pmc_m.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py --full $PMCARGS > $O/pmc_f.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py --full $PMCARGS > $O/pmc_w.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_m -- python3 bench.py --full $PMCARGS > $O/pmc_m.log 2>&1
 ( python3 tools/pmc_summary.py $O/pmc_f 14; python3 tools/pmc_summary.py $O/pmc_w 14 ) > $O/${TAG}_pmc_bench_E128.txt
 python3 tools/pmc_mfma_util.py $O/pmc_m 16 > $O/${TAG}_pmc_mfma_util.txt
 python3 tools/pmc_traffic_json.py $O/pmc_f $O/pmc_w 128 $RND $HEAD > $O/pmc_traffic.log 2>&1
@@ -35,7 +35,7 @@ for NS in 20 50; do
 done
 find $O -name "*.csv" -size +1M -delete
 # the default bench line LAST: profiles/pmc_traffic.json now belongs to this kernel source, so roofline.traffic is filled in
-python3 bench.py > $O/${TAG}_bench_E128.json 2> $O/bench.err
+python3 bench.py --full > $O/${TAG}_bench_E128.json 2> $O/bench.err
 tail -1 $O/${TAG}_bench_E128.json | cut -c1-400
 # power / clock: the step runs at the package power limit (hwmon sampling; no privileges needed)
 python3 tools/power_probe.py 128 5 2>&1 | grep -v amdgpu.ids > $O/${TAG}_power_probe.txt

@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/other_configs.txt}
 mkdir -p $(dirname $OUT); : > $OUT
 COMMON="--no-cpu-baseline --strong-episodes 0 --no-standalone --validate-episodes 0"
 run() {
-  python3 bench.py $1 $COMMON 2>/dev/null | tail -1 > /tmp/oc_line.json
+  python3 bench.py --full $1 $COMMON 2>/dev/null | tail -1 > /tmp/oc_line.json
   python3 - "$1" >> $OUT <<'PY'
 import json, sys
 try:

@@ -5,4 +5,4 @@ rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES 
 python tools/pmc_summary.py gpurun_out/pmcx2/b 60 | grep -E "conv_x3_kernel<128, 64" | cut -c1-60,100-170
 find gpurun_out/pmcx2 -name "*.csv" -size +2M -delete
 python tools/step_breakdown.py 128 20 2>&1 | grep -E "x3_bnstats|inner step"
-for k in 40 41 40 41; do MFT_X3_KNOBS=$k python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-120; done
+for k in 40 41 40 41; do MFT_X3_KNOBS=$k python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-120; done

@@ -7,8 +7,8 @@ python3 -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" |
 tail -6 $O/pytest.log
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 T0=$(date +%s)
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-echo "python bench.py wall: $(( $(date +%s) - T0 )) s"
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+echo "python bench.py --full wall: $(( $(date +%s) - T0 )) s"
 tail -1 $O/bench_default.json | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
@@ -18,7 +18,7 @@ print('strong',d['strong_scaling']['episodes_per_s'], d['strong_scaling'].get('e
 for k,v in (d.get('other_configs') or {}).items(): print(k, v.get('value'), v.get('ms_per_step'), (v.get('dominant') or {}).get('frac'), v.get('error'))
 "
 for K in 1 4; do
-  rocprofv3 --kernel-trace -d $O/tr$K --output-format csv -- python3 bench.py --workload metatrain --episodes-per-rank $K --steps 30 --warmup 5 --no-cpu-baseline > $O/run$K.log 2>&1
+  rocprofv3 --kernel-trace -d $O/tr$K --output-format csv -- python3 bench.py --full --workload metatrain --episodes-per-rank $K --steps 30 --warmup 5 --no-cpu-baseline > $O/run$K.log 2>&1
   f=$(find $O/tr$K -name "*kernel_trace.csv" | head -1)
   python3 tools/metatrain_graph_timeline.py "$f" > $O/metatrain_graph_timeline_k$K.txt
   head -3 $O/metatrain_graph_timeline_k$K.txt | cut -c1-200

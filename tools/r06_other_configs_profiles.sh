@@ -6,9 +6,9 @@ O=gpurun_out/r06_oc; rm -rf $O; mkdir -p $O
 COMMON="--no-cpu-baseline --no-standalone --strong-episodes 0 --validate-episodes 0 --no-other-configs"
 prof() {   # key, args...
   key=$1; shift
-  rocprofv3 --kernel-trace --stats -d $O/$key -o kt -- python3 bench.py "$@" $COMMON > $O/${key}_bench.json 2> $O/${key}.err
+  rocprofv3 --kernel-trace --stats -d $O/$key -o kt -- python3 bench.py --full "$@" $COMMON > $O/${key}_bench.json 2> $O/${key}.err
   db=$(find $O/$key -name "*.db" | head -1)
-  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py $* $COMMON   (MI355X, round-6 tree; every kernel, nothing cut)";
+  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full $* $COMMON   (MI355X, round-6 tree; every kernel, nothing cut)";
     echo "# bench line: $(tail -1 $O/${key}_bench.json | cut -c1-260)";
     python3 tools/rocpd_stats.py "$db"; } > $O/r06_other_configs_${key}_kernel_stats.txt
   find $O/$key -name "*.db" -delete

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/e64; mkdir -p $O; : > $O/out.txt
 COMMON="--no-cpu-baseline --strong-episodes 0 --no-standalone --validate-episodes 0"
 run() {
-  env $1 python3 bench.py $2 $COMMON 2>/dev/null | tail -1 | python3 -c "
+  env $1 python3 bench.py --full $2 $COMMON 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('%-44s %-34s -> %8.3f episodes/s %9.2f ms/batch fused=%s' % ('$1', '$2', d['value'], d['ms_per_step'], d['whole_path_hbm']['fused_next_forward']))" >> $O/out.txt
 }
