@@ -678,7 +678,8 @@ int mft_graph_aggregate_backward(const float* A, const float* x, int ldx, const 
                                  float* dA, int n_graphs, int N, int F, int accumulate, void* stream);
 int mft_build_graph_nodes_backward(const float* dnodes, int ld, float* dz, int zf, int n_episodes, int n_way,
                                    int n_support, int n_query, int fold, void* stream);
-/* (dbias, nullable [n_way]: column sums of dscores = the gradient of the bias of the layer that produced `out`, gnn.layer_last.fc) */
+/* (dbias, nullable [n_way]: column sums of dscores = the gradient of the bias of the layer that produced `out`, gnn.layer_last.fc;
+ * any n_way, ldo >= n_way) */
 int mft_gather_query_scores_backward(const float* dscores, float* dout, int ldo, int n_episodes, int n_way,
                                      int n_support, int n_query, float* dbias, void* stream);
 

@@ -653,21 +653,26 @@ __global__ __launch_bounds__(256) void gather_scores_bwd_kernel(const float* __r
     const long long total = rows * ldo;
     // dbias[k] (nullable) = column sums of d(out) = of dscores (every other row of d(out) is zero): the gradient of layer_last's
     // fc.bias (gnn.py:43-56; no BatchNorm behind it) by block 0 -- 16 row lanes x 16 columns, lanes combined in lane order (fixed
-    // summation order) -- instead of the two column-sum launches the backward otherwise spends on it
+    // summation order) -- instead of the two column-sum launches the backward otherwise spends on it.  n_way > 16: the 16 column
+    // lanes walk the columns 16 at a time (each column keeps the same summation order as a single chunk)
     if (dbias && blockIdx.x == 0) {
         __shared__ float red[16][17];
-        const int c = threadIdx.x & 15, rl = threadIdx.x >> 4;
+        const int rl = threadIdx.x >> 4;
         const long long nr = (long long)n_ep * n_way * nq;
-        float acc = 0.f;
-        if (c < n_way)
-            for (long long r = rl; r < nr; r += 16) acc += dscores[r * n_way + c];
-        red[rl][c] = acc;
-        __syncthreads();
-        if (rl == 0 && c < n_way) {
-            float t = red[0][c];
+        for (int c0 = 0; c0 < n_way; c0 += 16) {
+            const int c = c0 + (threadIdx.x & 15);
+            float acc = 0.f;
+            if (c < n_way)
+                for (long long r = rl; r < nr; r += 16) acc += dscores[r * n_way + c];
+            red[rl][threadIdx.x & 15] = acc;
+            __syncthreads();
+            if (rl == 0 && c < n_way) {
+                float t = red[0][c - c0];
 #pragma unroll
-            for (int j = 1; j < 16; ++j) t += red[j][c];
-            dbias[c] = t;
+                for (int j = 1; j < 16; ++j) t += red[j][c - c0];
+                dbias[c] = t;
+            }
+            __syncthreads();
         }
     }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -878,7 +883,7 @@ extern "C" int mft_build_graph_nodes_backward(const float* dnodes, int ld, float
 
 extern "C" int mft_gather_query_scores_backward(const float* dscores, float* dout, int ldo, int n_episodes, int n_way,
                                                 int n_support, int n_query, float* dbias, void* stream) {
-    if (dbias && n_way > 16) return MFT_EINVAL;
+    if (ldo < n_way) return MFT_EINVAL;
     const long long total = (long long)n_episodes * n_query * n_way * (n_support + 1) * ldo;
     hipLaunchKernelGGL(gather_scores_bwd_kernel, dim3(bgrid(total)), dim3(256), 0, (hipStream_t)stream, dscores, dout, ldo,
                        n_episodes, n_way, n_support, n_query, dbias);

@@ -923,10 +923,21 @@ def next_forward_ok(ipg, H6):
 
 # ------------------------------------------------------------------------------------------ GNN head
 
+MAX_N_WAY = 32     # the graph-node rows are 256 floats wide: the last Wcompute reads 128 + 2 * 48 + n_way columns of them
+
+
+def check_n_way(n_way):
+    """The GnnNet head's episode width limit, enforced before anything is packed or launched."""
+    if not 1 <= int(n_way) <= MAX_N_WAY:
+        raise ValueError("GnnNet head: n_way = %d is not supported (1 <= n_way <= %d: the graph-node rows hold 128 + 96 + n_way "
+                         "<= 256 features)" % (int(n_way), MAX_N_WAY))
+
+
 class GnnHeadWeights:
     """Packed device copy of GnnNet.fc and GnnNet.gnn (state dict keys 'fc.*', 'gnn.*')."""
 
     def __init__(self, sd, device, n_way):
+        check_n_way(n_way)
         self.n_way = n_way
         self.plan = ops.PackPlan()
         n_packed = [0]

@@ -588,7 +588,7 @@ def head_backward(G, t, dscores):
     dX = _empty((rows, 256), dev)              # first written (all 229 feature columns) by layer_last's aggregate backward: no zero fill
     d_out = _empty((rows, 32), dev)
     db_last = _empty((n_way,), dev)            # layer_last.fc.bias: the column sums of dscores, from the same launch
-    L.check(L.lib().mft_gather_query_scores_backward(ops._p(dscores.contiguous()), ops._p(d_out), 32, k, n_way, ns, nq,
+    L.check(L.lib().mft_gather_query_scores_backward(ops._p(dscores.contiguous()), ops._p(d_out), d_out.shape[1], k, n_way, ns, nq,
                                                      ops._p(db_last), ops._stream()), "mft_gather_query_scores_backward")
     wb = ops.WgradBatch(WGRAD_BATCH)            # the head's 16 weight gradients: registered as the pass goes, run together at its end
     if WGRAD_BATCH:

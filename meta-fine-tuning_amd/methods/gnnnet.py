@@ -37,6 +37,7 @@ class GnnNet(MetaTemplate):
     FOLD50 = False          # gnnnet_copy.GnnNet folds 50 supports to 25 graph nodes per class
 
     def __init__(self, model_func, n_way, n_support):
+        Fn.check_n_way(n_way)
         super().__init__(model_func, n_way, n_support)
         if self.maml:
             raise NotImplementedError("gnnnet_maml fast-weight layers are off the hot path (SURVEY.md §2.1)")

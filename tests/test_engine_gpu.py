@@ -141,14 +141,20 @@ def test_gnn_forward_full_graph_batches_vs_reference_golden(golden_dir, B, N):
     assert biggest <= B * (N * (N + 1) // 2) * 192, biggest
 
 
-@pytest.mark.parametrize("N,F", [(30, 133), (30, 181), (105, 229), (7, 133)])
+def _wcompute_layer(F):
+    """-> (n_way, Wcompute name) whose input is F features wide: 5-way at 133 / 181 / 229; F = 160 is layer_w0 of a 32-way head
+    (K = Kpad = 160), F = 256 its w_comp_last (K = Kpad = 256, the register-K layer's limit)."""
+    return {133: (5, "layer_w0"), 181: (5, "layer_w1"), 229: (5, "w_comp_last"), 160: (32, "layer_w0"), 256: (32, "w_comp_last")}[F]
+
+
+@pytest.mark.parametrize("N,F", [(30, 133), (30, 181), (105, 229), (7, 133), (64, 256), (33, 160)])
 def test_fused_pair_mlp_equals_materialised_wcompute(N, F, monkeypatch):
     """csrc/pair_mlp.hip (upper-triangle rows, |x_i - x_j| in the loader, BatchNorm from the epilogue statistics, BatchNorm +
     leaky_relu in the next loader) against the materialised sequence it replaces and against float64, two episodes of 3
     graphs with DIFFERENT statistics; also with the episodes processed in two chunks."""
-    sd = synthetic.gnn_head_state_dict(seed=5)
-    G = Fn.GnnHeadWeights(sd, DEV, 5)
-    name = {133: "layer_w0", 181: "layer_w1", 229: "w_comp_last"}[F]
+    n_way, name = _wcompute_layer(F)
+    sd = synthetic.gnn_head_state_dict(seed=5, n_way=n_way)
+    G = Fn.GnnHeadWeights(sd, DEV, n_way)
     rs = np.random.RandomState(N + F)
     B, groups = 6, 2
     nodes = rs.standard_normal((B, N, F)).astype(np.float32)
@@ -181,16 +187,17 @@ def test_fused_pair_mlp_equals_materialised_wcompute(N, F, monkeypatch):
     np.testing.assert_allclose(a_h.sum(2).cpu().numpy(), 1.0, atol=1e-5)
 
 
-@pytest.mark.parametrize("N,F,B,groups", [(30, 133, 32, 2), (30, 181, 16, 1), (30, 229, 16, 1), (7, 133, 6, 2), (26, 133, 9, 3)])
+@pytest.mark.parametrize("N,F,B,groups", [(30, 133, 32, 2), (30, 181, 16, 1), (30, 229, 16, 1), (7, 133, 6, 2), (26, 133, 9, 3),
+                                           (64, 256, 4, 2), (64, 160, 2, 1)])
 def test_register_k_pair_layers_match_tile_kernel_and_float64(N, F, B, groups, monkeypatch):
     """The register-K form of the Wcompute layers (mft_pair_mlp_layer_rk: 32-row tiles, the whole K in registers split over four
     waves -- what a meta-training step of one or a few episodes launches) against the 128-row tile kernel on the same inputs and
     against the float64 statement of gnn.py:78-115: same raw layer outputs / BatchNorm tables to rounding (another fixed
     summation order over k), A within the tile kernel's own error bound; run twice -> bit-identical."""
     from meta_fine_tuning_amd import functional_bwd as FB
-    sd = synthetic.gnn_head_state_dict(seed=5)
-    G = Fn.GnnHeadWeights(sd, DEV, 5)
-    name = {133: "layer_w0", 181: "layer_w1", 229: "w_comp_last"}[F]
+    n_way, name = _wcompute_layer(F)
+    sd = synthetic.gnn_head_state_dict(seed=5, n_way=n_way)
+    G = Fn.GnnHeadWeights(sd, DEV, n_way)
     rs = np.random.RandomState(N + F)
     nodes = rs.standard_normal((B, N, F)).astype(np.float32)
     gpg = B // groups

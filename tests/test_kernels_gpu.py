@@ -406,7 +406,9 @@ def test_adam_sgd_maml():
     assert torch.equal(ag.cpu(), a - (c - b))
 
 
-@pytest.mark.parametrize("B,N,Fd", [(15, 30, 133), (2, 105, 181), (2, 130, 229), (130, 30, 133), (128, 130, 229), (129, 7, 181)])
+@pytest.mark.parametrize("B,N,Fd", [(15, 30, 133), (2, 105, 181), (2, 130, 229), (130, 30, 133), (128, 130, 229), (129, 7, 181),
+                                    # other episode widths: F = 128 + n_way (+ 48 / 96) at n_way = 2 / 20 / 32, N = 64 / 65 / 260
+                                    (16, 4, 130), (4, 120, 148), (2, 64, 160), (2, 64, 256), (6, 65, 141), (2, 260, 138)])
 def test_gnn_glue(B, N, Fd):
     # B >= 128 graphs: mft_graph_aggregate's one-workgroup-per-graph form with x[b] staged in LDS
     ld = 256
@@ -416,7 +418,7 @@ def test_gnn_glue(B, N, Fd):
     d = ops.pair_absdiff(x.to(DEV), N, Fd, Kp)
     xv = x[:, :Fd].view(B, N, Fd)
     ref = (xv.unsqueeze(2) - xv.unsqueeze(1)).abs().reshape(B * N * N, Fd)
-    assert torch.equal(d.cpu()[:, :Fd], ref) and float(d.cpu()[:, Fd:].abs().max()) == 0.0
+    assert torch.equal(d.cpu()[:, :Fd], ref) and float(d.cpu()[:, Fd:].abs().sum()) == 0.0         # (no padding when Fd % 32 == 0)
     s = torch.zeros(B * N * N, 4)
     s[:, 0] = rnd((B * N * N,), 36) * 2
     A = ops.masked_softmax(s.to(DEV), N)
@@ -426,7 +428,7 @@ def test_gnn_glue(B, N, Fd):
     y = ops.graph_aggregate(A, x.to(DEV), Fd, ops.round_up(2 * Fd, 32))
     yref = torch.cat([xv.double(), torch.bmm(A.cpu().double(), xv.double())], 2).view(B * N, 2 * Fd)
     assert float((y.cpu().double()[:, :2 * Fd] - yref).abs().max()) < 1e-5
-    assert float(y.cpu()[:, 2 * Fd:].abs().max()) == 0.0
+    assert float(y.cpu()[:, 2 * Fd:].abs().sum()) == 0.0
     z = torch.zeros(B * N, ld, device=DEV)
     ops.copy_cols(y, z, 7, 48, act=ops.ACT_LRELU)
     assert float((z.cpu()[:, 7:55].double() - F.leaky_relu(y.cpu()[:, :48].double(), 0.01)).abs().max()) < 1e-7
@@ -1569,3 +1571,28 @@ def test_bn_stats_and_backward_multi_are_bit_identical_to_single_launches(rows, 
     rb_ = FB.bn_bwd(xb, dy, C, rows, mb, sb, gb, y_act=ya, act=ops.ACT_RELU, groups=groups)
     for got, ref in zip((dxa, dga, dba, dxb, dgb, dbb), ra_ + rb_):
         assert torch.equal(got, ref)
+
+
+@pytest.mark.parametrize("n_way,ns,nq,ep,ldo", [(2, 1, 16, 1, 32), (5, 5, 16, 1, 32), (16, 5, 5, 2, 32), (17, 1, 4, 1, 32),
+                                                 (32, 1, 2, 2, 32), (20, 5, 4, 1, 48)])
+def test_gather_query_scores_backward(n_way, ns, nq, ep, ldo):
+    """mft_gather_query_scores_backward: d(out) [ep * nq graphs x n_way * (ns+1) nodes, ldo] = dscores scattered to each graph's
+    query node (zero everywhere else, the padding columns included) and dbias = the column sums of dscores, against float64 --
+    at n_way past the 16 column lanes of the one-workgroup column sum too."""
+    from meta_fine_tuning_amd import _lib
+    rows = ep * n_way * nq
+    ds = rnd((rows, n_way), 90 + n_way)
+    dd = ds.to(DEV)
+    dout = torch.full((ep * nq * n_way * (ns + 1), ldo), float("nan"), device=DEV)
+    dbias = torch.full((n_way,), float("nan"), device=DEV)
+    _lib.check(_lib.lib().mft_gather_query_scores_backward(ops._p(dd), ops._p(dout), ldo, ep, n_way, ns, nq, ops._p(dbias),
+                                                            ops._stream()), "mft_gather_query_scores_backward")
+    ref = torch.zeros(ep, nq, n_way, ns + 1, ldo, dtype=torch.float64)
+    # scores row (e * n_way + c) * nq + q is query q of class c in episode e; its graph is (e, q), its node (c, ns)
+    ref[:, :, :, ns, :n_way] = ds.double().view(ep, n_way, nq, n_way).permute(0, 2, 1, 3)
+    assert torch.equal(dout.cpu().double().view_as(ref), ref)
+    colsum = ds.double().sum(0)
+    assert float((dbias.cpu().double() - colsum).abs().max()) < 1e-5 * max(1.0, float(ds.abs().sum(0).max()))
+    # a row stride narrower than the scores is refused
+    assert _lib.lib().mft_gather_query_scores_backward(ops._p(dd), ops._p(dout), n_way - 1, ep, n_way, ns, nq, ops._p(dbias),
+                                                        ops._stream()) != 0

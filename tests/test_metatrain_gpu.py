@@ -486,17 +486,18 @@ def test_one_launch_repack_after_in_place_update():
     assert AG.module_weights(model2.feature) is not W0
 
 
-@pytest.mark.parametrize("variant", ["gnnnet", "gnnnet_copy"])
+@pytest.mark.parametrize("variant", ["gnnnet", "gnnnet_copy", "gnnnet_20way"])
 def test_graphed_episode_loop_is_bit_identical(variant, capsys, monkeypatch):
     """MetaTemplate's episode loop (meta_template.py:76-92) with forward + backward replayed from ONE hipGraph after three eager
     steps (graph_step.GraphedLossBackward) against the plain loop: the printed loss lines and every parameter after 9 steps
     with the fused outer Adam must match bit for bit -- also after the loader changes the episode's shape (recapture) and when
-    the optimizer runs between replays."""
+    the optimizer runs between replays.  ``gnnnet_20way``: 20-way 5-shot at train.py's 4 queries (then 3)."""
     from meta_fine_tuning_amd import graph_step, optim
     from meta_fine_tuning_amd.methods import gnnnet_copy
-    cls, n_shot, size = (GnnNet, 5, 84) if variant == "gnnnet" else (gnnnet_copy.GnnNet, 50, 42)
-    eps = [synthetic.train_episode(700 + i, 5, n_shot, 16, size) for i in range(5)]              # host tensors, as a DataLoader yields
-    eps += [synthetic.train_episode(710 + i, 5, n_shot, 12, size) for i in range(4)]             # the loader switches to 12 queries
+    cls, n_way, n_shot, size, nq = {"gnnnet": (GnnNet, 5, 5, 84, (16, 12)), "gnnnet_copy": (gnnnet_copy.GnnNet, 5, 50, 42, (16, 12)),
+                                    "gnnnet_20way": (GnnNet, 20, 5, 84, (4, 3))}[variant]
+    eps = [synthetic.train_episode(700 + i, n_way, n_shot, nq[0], size) for i in range(5)]       # host tensors, as a DataLoader yields
+    eps += [synthetic.train_episode(710 + i, n_way, n_shot, nq[1], size) for i in range(4)]      # the loader switches to fewer queries
 
     class Loader:
         def __len__(self):
@@ -509,12 +510,12 @@ def test_graphed_episode_loop_is_bit_identical(variant, capsys, monkeypatch):
     def run(graphed):
         monkeypatch.setattr(graph_step, "ENABLED", graphed)
         torch.manual_seed(0)
-        model = cls(model_dict['ResNet10'], n_way=5, n_support=n_shot).cuda()
-        model.load_state_dict(synthetic.gnnnet_state_dict(seed=27))
+        model = cls(model_dict['ResNet10'], n_way=n_way, n_support=n_shot).cuda()
+        model.load_state_dict(synthetic.gnnnet_state_dict(seed=27, n_way=n_way))
         model.train()
         opt = optim.Adam(model.parameters())
         capsys.readouterr()
-        (model.train_loop if variant == "gnnnet" else model.train_loop50)(0, Loader(), opt)
+        (model.train_loop50 if variant == "gnnnet_copy" else model.train_loop)(0, Loader(), opt)
         out = capsys.readouterr().out
         st = model.__dict__.get("_mft_graph_steps", {}).get("set_forward_loss")
         return out, [p.detach().clone() for p in model.parameters()], [b.detach().clone() for b in model.buffers()], st

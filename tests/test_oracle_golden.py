@@ -89,6 +89,41 @@ def test_g3_set_forward_and_grads(golden_dir):
     np.testing.assert_allclose(s32.numpy(), g["scores"], atol=2e-5)
 
 
+G21_SHAPES = [(20, 5, 4, 41, 51), (32, 1, 2, 42, 52), (3, 4, 4, 43, 53), (5, 20, 16, 44, 54)]     # = oracle/make_golden_g21.py SHAPES
+
+
+@pytest.mark.parametrize("n_way,n_shot,n_query,wseed,xseed", G21_SHAPES)
+def test_g21_episode_shapes(golden_dir, n_way, n_shot, n_query, wseed, xseed):
+    """The oracle's meta-training loss and gradients in fp64 against the reference's fp32 GnnNet.set_forward_loss + backward at
+    episode shapes other than 5-way 5-shot (G21): pins the oracle at the widths the GPU tests of tests/test_episode_shapes_gpu.py
+    and the 20-shot step compare against.  Same bars as G3."""
+    g = _g(golden_dir, "g21_episode_shapes.npz")
+    assert [tuple(r) for r in g["shapes"].tolist()] == G21_SHAPES
+    t = "%dw%ds%dq" % (n_way, n_shot, n_query)
+    dt = torch.float64
+    sd = O.clone_state(synthetic.gnnnet_state_dict(seed=wseed, n_way=n_way), dt)
+    x = synthetic.train_episode(xseed, n_way, n_shot, n_query, 84).to(dt)
+    pkeys = [k for k, v in sd.items() if v.is_floating_point() and "running" not in k]
+    for k in pkeys:
+        sd[k].requires_grad_(True)
+    loss, scores = O.meta_train_loss(sd, x, n_way, n_shot)
+    assert scores.shape == (n_way * n_query, n_way)
+    np.testing.assert_allclose(scores.detach().numpy(), g["scores_" + t], atol=2e-5)
+    assert abs(float(loss.detach()) - float(g["loss_" + t])) < 1e-5
+    grads = torch.autograd.grad(loss, [sd[k] for k in pkeys])
+    gn = {k: float(v.norm()) for k, v in zip(pkeys, grads)}
+    assert sorted(gn) == [str(n) for n in g["gradnames_" + t]]
+    for name, ref in zip(g["gradnames_" + t], g["gradnorms_" + t]):
+        if gn[str(name)] < 1e-9:                # a bias in front of a BatchNorm: zero in fp64, the reference's fp32 rounding noise
+            assert ref < 1e-5, name
+            continue
+        assert abs(gn[str(name)] - ref) <= 1e-3 * ref + 1e-7, name
+    gd = dict(zip(pkeys, grads))
+    np.testing.assert_allclose(gd["fc.0.weight"][:4, :8].numpy(), g["grad_fc0w_slice_" + t], atol=1e-5)
+    np.testing.assert_allclose(gd["gnn.layer_last.fc.weight"][:, :8].numpy(), g["grad_lastw_slice_" + t], atol=1e-5)
+    np.testing.assert_allclose(gd["gnn.layer_last.fc.bias"].numpy(), g["grad_lastb_" + t], atol=1e-6)
+
+
 @pytest.mark.parametrize("tag,dt", [("f32", torch.float32), ("f64", torch.float64)])
 def test_g4_inner_loop(golden_dir, tag, dt):
     g = _g(golden_dir, "g4_inner_loop.npz")
