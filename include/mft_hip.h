@@ -450,6 +450,19 @@ int mft_cross_entropy_mean_backward(const float* logits, int ld, const void* lab
                                     const float* grad_loss, float* dlogits, int ldd, void* stream);
 int mft_softmax_rows(const float* x, int ldx, float* y, int ldy, int C, int rows, void* stream);
 
+/* ProtoNet head (methods/protonet.py set_forward / euclidean_dist), all episodes of a step in ONE launch each way, one workgroup
+ * per episode.  feats [episodes, n_way, n_support + n_query, D] (row stride ld); query rows class-major (c * n_query + q).
+ * scores [episodes * n_way * n_query, n_way]: -sum_d (q_d - p_cd)^2 in fp32, p_c = (sum of class c's support rows in row
+ * order) / n_support; softmax = 1: row softmax of the scores instead (finetune.py:316-317).
+ * backward: dfeats (same layout, row stride ldd) for EVERY row -- query rows -2 sum_c g_qc (q - p_c), support rows of class c
+ * (sum_q 2 g_qc (q - p_c)) / n_support; no atomics, fixed summation order.  dscores row stride ldg >= n_way.
+ * MFT_EINVAL outside n_way 1..64, n_support >= 1, n_query >= 1, D <= 512 a multiple of 4, ld / ldd multiples of 4,
+ * 16-byte aligned feats / dfeats. */
+int mft_proto_scores(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, float* scores,
+                     int softmax, void* stream);
+int mft_proto_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
+                       const float* dscores, int ldg, float* dfeats, int ldd, void* stream);
+
 /* optimisers --------------------------------------------------------------------------- */
 /* torch.optim.Adam.step (finetune.py:255,299; gnnnet.py:128,177; train.py:28), one flat slab of n floats:
  * g += wd*p; m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g*g; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps) */

@@ -77,6 +77,8 @@ SIGNATURES = {
     "mft_avgpool_relu_backward": [_P, _P, _P, _I, _I, _I, _P],
     "mft_cross_entropy": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
     "mft_softmax_rows": [_P, _I, _P, _I, _I, _I, _P],
+    "mft_proto_scores": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    "mft_proto_backward": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     "mft_cross_entropy_mean": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
     "mft_cross_entropy_mean_backward": [_P, _I, _P, _I, _I, _I, _P, _P, _I, _P],
     "mft_adam_step": [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P],

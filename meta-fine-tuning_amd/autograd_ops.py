@@ -329,3 +329,32 @@ def gnnnet_head(model, feats, n_support, n_query, fold=False, episodes=1):
     G = head_weights(model.gnn, model.fc, model.n_way)
     f = feats.detach().contiguous().float()
     return Fn.gnnnet_scores(G, f, episodes, model.n_way, n_support, n_query, arena_for(f.device), fold=fold, tag="head%d" % episodes).clone()
+
+
+class _ProtoHeadFn(torch.autograd.Function):
+    """ProtoNet prototypes + negative squared euclidean distances (protonet.py set_forward / euclidean_dist) with a HIP backward:
+    one mft_proto_scores launch forward, one mft_proto_backward launch back, all episodes at once."""
+
+    @staticmethod
+    def forward(ctx, feats, n_way, n_support, n_query, episodes):
+        ctx.save_for_backward(feats)
+        ctx.shape = (episodes, n_way, n_support, n_query)
+        return ops.proto_scores(feats, episodes, n_way, n_support, n_query)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, = ctx.saved_tensors
+        episodes, n_way, n_support, n_query = ctx.shape
+        d = dscores if (dscores.dtype == torch.float32 and dscores.is_contiguous()) else dscores.contiguous().float()
+        return ops.proto_backward(feats, d, episodes, n_way, n_support, n_query), None, None, None, None
+
+
+def protonet_head(feats, n_way, n_support, n_query, episodes=1):
+    """ProtoNet.set_forward tail (protonet.py): feats [episodes*n_way*(n_support+n_query), D] (class-major rows, one episode after
+    the other) -> scores [episodes*n_way*n_query, n_way] = -||q - mean(support_c)||^2.  Differentiable when autograd records."""
+    _require_cuda(feats, "ProtoNet head")
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and feats.requires_grad:
+        return _ProtoHeadFn.apply(feats, n_way, n_support, n_query, episodes)
+    return ops.proto_scores(feats.detach(), episodes, n_way, n_support, n_query)

@@ -286,13 +286,16 @@ class FinetuneEngine:
         ``head_state`` overrides the fc/gnn weights (the reference scores with the *loaded model*, finetune.py:316).
         ``mode`` "gnn": finetune.finetune (inner loss on the raw feature, GNN scoring);
         "linear": finetune.finetune_linear (finetune.py:45-174: per-episode Linear(512, n_way) classifier trained together
-        with the last block over the ORIGINAL support images only; scores = softmax(classifier(features)))."""
-        assert mode in ("gnn", "linear")
+        with the last block over the ORIGINAL support images only; scores = softmax(classifier(features)));
+        "proto": finetune.finetune with a ProtoNet model -- the inner loop of "gnn" unchanged, scores = softmax of the ProtoNet
+        head on the final-pass features (mft_proto_scores with its softmax epilogue; ``state`` needs only 'feature.*')."""
+        assert mode in ("gnn", "linear", "proto")
         self.mode = mode
+        self.views = mode != "linear"      # the inner loop trains on every view (finetune()); "linear" on view 0 only
         # ``graph``: capture one inner step (single stream) as a hipGraph and replay it for every step -- ~40 launches
         # become 3 (index copy, label copy, replay).  Measured: no gain (a step is a chain of dependent kernels bound by
         # per-kernel latency on the GPU, not by the host launch rate; DESIGN.md section 2); off by default.
-        self.use_graph = bool(graph) and mode == "gnn" and fused_adam
+        self.use_graph = bool(graph) and self.views and fused_adam
         if self.use_graph:
             pipeline = False
         self._graphs = {}
@@ -340,7 +343,7 @@ class FinetuneEngine:
         self.fused_adam = fused_adam
         self.n_per_view = n_way * n_support
         # finetune.py:214-233,269: view 0 twice + every other view; finetune_linear permutes support_size only (:139-141)
-        self.n_total = self.n_per_view * (n_views + 1) if mode == "gnn" else self.n_per_view
+        self.n_total = self.n_per_view * (n_views + 1) if self.views else self.n_per_view
         self.n_all = n_way * (n_support + n_query)
         fsd = {k[len("feature."):]: v for k, v in state.items()
                if k.startswith("feature.") and not k.startswith(("feature2.", "feature3."))}
@@ -417,7 +420,7 @@ class FinetuneEngine:
         self.Xs = torch.empty((self.E * self.n_total, px), device=self.dev)       # support store, NHWC rows
         self.Xall = torch.empty((self.E * self.n_all, image_size, image_size, 3), device=self.dev)
         ya = np.repeat(np.arange(n_way), n_support)
-        self.y_support = (np.tile(ya, n_views + 1) if mode == "gnn" else ya).astype(np.int32)
+        self.y_support = (np.tile(ya, n_views + 1) if self.views else ya).astype(np.int32)
         # every support image is drawn once per epoch: with >1 epoch cache its (mini-batch independent) stem conv
         if stem_cache:
             # 64 channels x (H/2)^2 fp32 per resident support image: 226 KB at 84x84, 3.2 MB at 224x224.  Keep the cache
@@ -446,11 +449,11 @@ class FinetuneEngine:
         assert len(liz_x) == self.n_views
         views = [liz_x[0].to(self.dev, non_blocking=True)]
         assert views[0].shape[1] == ns + self.n_query
-        if self.mode == "gnn":
+        if self.views:
             views += [xv.to(self.dev, non_blocking=True) for xv in liz_x[1:]]
         views = [v if (v.dtype == torch.float32 and v.is_contiguous()) else v.float().contiguous() for v in views]
         ptrs = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-        rc = ops._lib.lib().mft_ingest_episode_views(ptrs, len(views), 1 if self.mode == "gnn" else 0, self.n_way,
+        rc = ops._lib.lib().mft_ingest_episode_views(ptrs, len(views), 1 if self.views else 0, self.n_way,
                                                      ns + self.n_query, ns, 3, H, H, ops._p(Xs[slot * self.n_total]),
                                                      ops._p(Xall[slot * self.n_all]), ops._stream())
         ops._lib.check(rc, "mft_ingest_episode_views")
@@ -465,7 +468,7 @@ class FinetuneEngine:
         Xs = self.Xs if Xs is None else Xs
         Xall = self.Xall if Xall is None else Xall
         ns, npv, H = self.n_support, self.n_per_view, self.size
-        assert self.mode == "gnn" and params.shape[0] == self.n_views
+        assert self.views and params.shape[0] == self.n_views
         src = src_u8.to(self.dev)
         n_way, per, Hs, Ws, _ = src.shape
         assert n_way == self.n_way and per == ns + self.n_query
@@ -730,6 +733,10 @@ class FinetuneEngine:
             ops._lib.check(rc, "mft_linear_head_scores")
             sc = sc.view(self.E, self.n_way, self.n_support + self.n_query, self.n_way)[:, :, self.n_support:]
             return sc.reshape(self.E, self.n_way * self.n_query, self.n_way), feats
+        if self.mode == "proto":
+            # (a fresh tensor, as softmax_rows gives the gnn path: a deferred final pass must not overwrite the previous batch's)
+            sc = ops.proto_scores(feats, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
+            return sc.view(self.E, self.n_way * self.n_query, self.n_way), feats
         ns = self.n_support // 2 if self.fold50 else self.n_support
         scores = Fn.gnnnet_scores(self.G, feats, self.E, self.n_way, ns, self.n_query, arena, fold=self.fold50)
         return ops.softmax_rows(scores).view(self.E, self.n_way * self.n_query, self.n_way), feats
@@ -807,7 +814,7 @@ class FinetuneEngine:
         stem cache are enqueued now on a fourth stream and swapped in when that call arrives with the same list object."""
         n = len(episodes)
         assert 0 < n <= self.E
-        defer_final = defer_final and self.mode == "gnn" and not self.use_graph and not return_feats
+        defer_final = defer_final and self.views and not self.use_graph and not return_feats
         if defer_final:
             self._flip_buffers()
         if perms is None:

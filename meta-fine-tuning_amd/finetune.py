@@ -98,6 +98,16 @@ def _head_key(model):
 
 
 def _engine_for(state_in, model, n_way, n_support, n_query, size, n_views, epochs, E, fold50=False):
+    """The finetune() engine for ``model``: a ProtoNet scores with its prototype head (mode "proto": no head weights, the key
+    says so), anything else with the GNN head of its fc / gnn modules."""
+    from .methods.protonet import ProtoNet
+    if isinstance(model, ProtoNet):
+        cfg = ("proto", n_way, n_support, n_query, size, n_views, epochs, E)
+
+        def build_proto():
+            return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
+                                      episodes_per_batch=E, mode="proto")
+        return _ENGINES.get(state_in, cfg, build_proto)
     cfg = ("gnn", _head_key(model), n_way, n_support, n_query, size, n_views, epochs, E, fold50)
 
     def build():
@@ -282,7 +292,7 @@ def draw_episode_perms(method, n_way, n_support, n_views, fine_tune_epoch, rng=n
     lin = gnn = None
     if method in ("all", "baseline"):
         lin = [rng.permutation(n_way * n_support) for _ in range(LINEAR_EPOCHS)]
-    if method in ("all", "gnnnet"):
+    if method in ("all", "gnnnet", "protonet"):
         gnn = [rng.permutation(n_way * n_support * (n_views + 1)) for _ in range(fine_tune_epoch)]
     return lin, gnn
 
@@ -324,7 +334,7 @@ def finetune_linear_batched(episodes, state_in, n_way=5, n_support=5, episodes_p
 def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch, n_way=5, n_support=5, episodes_per_batch=32,
                    rngs=None, classifiers=None, parts=False):
     """What the reference's loop body computes for each episode of ``episodes`` (finetune.py:615-619,647-649), in lockstep:
-    ``gnnnet`` -> finetune(); ``baseline`` -> finetune_linear(); ``all`` -> their sum.  The permutations of all episodes are
+    ``gnnnet`` / ``protonet`` -> finetune(); ``baseline`` -> finetune_linear(); ``all`` -> their sum.  The permutations of all episodes are
     drawn FIRST, episode by episode in the order the sequential calls would draw them (from the global numpy RNG, or from
     ``rngs[i]`` -- one generator per episode, the rank-count-invariant stream of parallel.episode_rng).
     ``parts``: return (linear scores | None, gnn scores | None) instead of the sum."""
@@ -338,7 +348,7 @@ def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch,
     s_lin = s_gnn = None
     if method in ("all", "baseline"):
         s_lin = finetune_linear_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, classifiers=classifiers)
-    if method in ("all", "gnnnet"):
+    if method in ("all", "gnnnet", "protonet"):
         s_gnn = finetune_batched(episodes, model, state_gnn, fine_tune_epoch, n_way, n_support, episodes_per_batch, perms=gnn_p)
     if parts:
         return s_lin, s_gnn
@@ -514,7 +524,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             return
         ids = batches[bi]
         if sampler is not None:
-            pipe = (method == "gnnnet" and not freeze_backbone and model is not None)
+            pipe = (method in ("gnnnet", "protonet") and not freeze_backbone and model is not None)
             eps = []
             for i in ids:
                 src, P, _ = sampler.episode(seed0 + i, size, gen_examples)
@@ -549,7 +559,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             ev.record()
         gens[bi] = (eps, ev, bad)
 
-    pipelined = (method == "gnnnet" and not freeze_backbone and model is not None)
+    pipelined = (method in ("gnnnet", "protonet") and not freeze_backbone and model is not None)
     n_views = 2 + gen_examples
     engine = None
     flags, score_chunks = [], []

@@ -36,7 +36,7 @@ _PER_SCRIPT = {
         ("--start_epoch", dict(default=0, type=int, help="Starting epoch")),
         ("--stop_epoch", dict(default=400, type=int, help="Stopping epoch")),
         # (not in the reference: k episodes per optimizer step in lockstep on one GPU = the update of a k-rank episode-parallel run)
-        ("--episodes_per_rank", dict(default=1, type=int, help="gnnnet without --fine_tune: episodes per optimizer step (lockstep)")),
+        ("--episodes_per_rank", dict(default=1, type=int, help="gnnnet / protonet without --fine_tune: episodes per optimizer step (lockstep)")),
     ],
     "save_features": [("--split", dict(default="novel", help="base/val/novel"))],
     "test": [

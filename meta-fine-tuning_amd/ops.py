@@ -847,6 +847,42 @@ def softmax_rows(x):
     return y
 
 
+def _proto_check(feats, episodes, n_way, n_support, n_query):
+    _f32c(feats)
+    if feats.dim() != 2 or feats.shape[0] != episodes * n_way * (n_support + n_query):
+        raise ValueError("ProtoNet head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, D]"
+                         % (tuple(feats.shape), episodes * n_way * (n_support + n_query)))
+
+
+def proto_scores(feats, episodes, n_way, n_support, n_query, softmax=False, out=None):
+    """ProtoNet scores (methods/protonet.py set_forward): feats [episodes*n_way*(n_support+n_query), D] (class-major rows, one
+    episode after the other) -> [episodes*n_way*n_query, n_way] = -||q - p_c||^2; ``softmax``: their row softmax instead."""
+    _proto_check(feats, episodes, n_way, n_support, n_query)
+    D = feats.shape[1]
+    rows = episodes * n_way * n_query
+    if out is not None and (tuple(out.shape) != (rows, n_way) or not out.is_contiguous()):
+        raise ValueError("proto_scores: out must be a contiguous [%d, %d] tensor" % (rows, n_way))
+    y = out if out is not None else torch.empty((rows, n_way), device=feats.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mft_proto_scores(_p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(y),
+                                           1 if softmax else 0, _stream()), "mft_proto_scores")
+    return y
+
+
+def proto_backward(feats, dscores, episodes, n_way, n_support, n_query, out=None):
+    """d(scores) -> d(feats) for every row of every episode (one launch, no zero fill)."""
+    _proto_check(feats, episodes, n_way, n_support, n_query)
+    _f32c(dscores)
+    if tuple(dscores.shape) != (episodes * n_way * n_query, n_way):
+        raise ValueError("proto_backward: dscores is %s, expected [%d, %d]" % (tuple(dscores.shape), episodes * n_way * n_query, n_way))
+    if out is not None and (out.shape != feats.shape or not out.is_contiguous()):
+        raise ValueError("proto_backward: out must be a contiguous tensor shaped like feats")
+    D = feats.shape[1]
+    dx = out if out is not None else torch.empty((feats.shape[0], D), device=feats.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mft_proto_backward(_p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(dscores),
+                                             dscores.stride(0), _p(dx), dx.stride(0), _stream()), "mft_proto_backward")
+    return dx
+
+
 def adam_hyper_advance(step_i32, hyper, lr=0.01, beta1=0.9, beta2=0.999):
     """Device-side t = ++step; hyper = {lr/(1-beta1^t), 1/sqrt(1-beta2^t)} (one tiny launch; graph-capturable)."""
     _lib.check(_lib.lib().mft_adam_hyper_advance(_p(step_i32), _p(hyper), lr, beta1, beta2, _stream()), "mft_adam_hyper_advance")

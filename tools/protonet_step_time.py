@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Milliseconds per graphed meta-training step (set_forward_loss + backward replayed from one hipGraph, then the fused outer Adam;
+MetaTemplate._episode_loop) of ProtoNet next to GnnNet, 5-way 5-shot 16 queries at 84 x 84, one episode per step (k = 1) and four
+episodes in lockstep (k = 4, train.py --episodes_per_rank 4); then the head's two launches alone (mft_proto_scores,
+mft_proto_backward) at 1, 4 and 32 episodes.
+    python tools/protonet_step_time.py [steps]"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import meta_fine_tuning_amd  # noqa: E402,F401
+from meta_fine_tuning_amd import graph_step, optim, synthetic  # noqa: E402
+from meta_fine_tuning_amd.io_utils import model_dict  # noqa: E402
+from meta_fine_tuning_amd.methods.gnnnet import GnnNet  # noqa: E402
+from meta_fine_tuning_amd.methods.protonet import ProtoNet  # noqa: E402
+
+steps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+
+
+def run(cls, k):
+    torch.manual_seed(0)
+    model = cls(model_dict["ResNet10"], n_way=5, n_support=5).cuda()
+    sd = synthetic.gnnnet_state_dict(seed=0)
+    model.load_state_dict({n: v for n, v in sd.items() if n in model.state_dict()})
+    model.train()
+    model.n_query = 16
+    opt = optim.Adam(model.parameters())
+    eps = [synthetic.train_episode(5000 + i, 5, 5, 16, 84) for i in range(2 * k)]
+    xs = [torch.stack(eps[j * k:(j + 1) * k]).cuda() if k > 1 else eps[j].cuda() for j in range(2)]
+    loss_fn = model.set_forward_loss_lockstep if k > 1 else model.set_forward_loss
+    step = graph_step.for_loop(model, loss_fn)
+    assert step is not None, "graphed steps are disabled (MFT_TRAIN_GRAPH)"
+    for i in range(6):                                   # eager warm-up, capture, first replays
+        step(xs[i % 2], opt)
+        opt.step()
+    torch.cuda.synchronize()
+    assert step.graph is not None and not step.failed
+    t0 = time.perf_counter()
+    for i in range(steps):
+        loss = step(xs[i % 2], opt)
+        opt.step()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / steps
+    print("%-8s k = %d  %7.3f ms per step  %7.1f episodes/s  loss %.5f" % (cls.__name__, k, dt * 1e3, k / dt, float(loss.detach())), flush=True)
+
+
+def head_launches(E, reps=200):
+    from meta_fine_tuning_amd import ops
+    f = torch.randn(E * 5 * 21, 512, device="cuda")
+    g = torch.randn(E * 5 * 16, 5, device="cuda")
+    sc = torch.empty(E * 5 * 16, 5, device="cuda")
+    dx = torch.empty_like(f)
+    out = []
+    for fn in (lambda: ops.proto_scores(f, E, 5, 5, 16, out=sc), lambda: ops.proto_backward(f, g, E, 5, 5, 16, out=dx)):
+        for _ in range(10):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) / reps * 1e3)
+    print("head launches, %2d episodes of 5-way 5-shot 16 queries: scores %6.1f us, backward %6.1f us (back-to-back average)"
+          % (E, out[0], out[1]), flush=True)
+
+
+for k in (1, 4):
+    for cls in (ProtoNet, GnnNet):
+        run(cls, k)
+for E in (1, 4, 32):
+    head_launches(E)
