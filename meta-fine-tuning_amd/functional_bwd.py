@@ -207,8 +207,10 @@ def resnet10_forward_taped(W, x, running=None, groups=1):
     return feat, t
 
 
-def resnet10_backward(W, t, dfeat, need):
-    """Gradients of every ResNet10 parameter named in ``need`` (set of 'trunk.*' keys) in reference layouts."""
+def resnet10_backward(W, t, dfeat, need, act_grads=None):
+    """Gradients of every ResNet10 parameter named in ``need`` (set of 'trunk.*' keys) in reference layouts.
+    ``act_grads`` (a dict, tests only): receives every block's activation gradients as 'trunk.N.out' (incoming, w.r.t. the block's
+    output) and 'trunk.N.in' (outgoing, w.r.t. its input) -- references to the pass's own tensors, no copy and no launch."""
     n, groups = t["n"], t.get("groups", 1)
     dev = dfeat.device
     grads = {}
@@ -226,6 +228,8 @@ def resnet10_backward(W, t, dfeat, need):
     for b in reversed(t["blocks"]):
         p, cin, cout, stride, rows = b["p"], b["cin"], b["cout"], b["stride"], b["rows"]
         x_in, out = b["x"], b["out"]
+        if act_grads is not None:
+            act_grads[p + ".out"] = d_out
         H_in = x_in.shape[1]
         o2 = out.view(-1, cout)
         d2 = d_out.view(-1, cout)
@@ -262,6 +266,8 @@ def resnet10_backward(W, t, dfeat, need):
             act_backward(dxs.view(-1, cin), dxs.view(-1, cin), dx.view(-1, cin), cin, NONE, True)
         else:
             act_backward(d2, o2, dx.view(-1, cin), cin, RELU, True)            # identity shortcut through relu2
+        if act_grads is not None:
+            act_grads[p + ".in"] = dx
         d_out = dx
     # stem: maxpool + relu backward, BatchNorm backward, 7x7 wgrad
     c0, a0 = t["c0"], t["a0"]

@@ -40,6 +40,17 @@ CONV_SHAPES = [
     ("trunk.7.shortcut", 256, 512, 1, 2, 0, 6),
     ("trunk.7.C2@224", 512, 512, 3, 1, 1, 7),
     ("trunk.0@224", 3, 64, 7, 2, 3, 224),
+    # the other layers of a 224 x 224 image (map sides 56 / 28 / 14: stride-2 layers start from EVEN sides, the last tap never reaches
+    # the right padding)
+    ("trunk.4.C1@224", 64, 64, 3, 1, 1, 56),
+    ("trunk.5.C1@224", 64, 128, 3, 2, 1, 56),
+    ("trunk.5.C2@224", 128, 128, 3, 1, 1, 28),
+    ("trunk.5.shortcut@224", 64, 128, 1, 2, 0, 56),
+    ("trunk.6.C1@224", 128, 256, 3, 2, 1, 28),
+    ("trunk.6.C2@224", 256, 256, 3, 1, 1, 14),
+    ("trunk.6.shortcut@224", 128, 256, 1, 2, 0, 28),
+    ("trunk.7.C1@224", 256, 512, 3, 2, 1, 14),
+    ("trunk.7.shortcut@224", 256, 512, 1, 2, 0, 14),
 ]
 
 
@@ -201,7 +212,8 @@ def test_conv2d_wgrad(Cin, Cout, k, stride, pad, H, G, ipg):
 
 
 @pytest.mark.parametrize("rows,C,G", [(45, 512, 4), (2205, 64, 3), (8820, 64, 1), (13500, 192, 1), (450, 48, 2),
-                                      (100, 128, 1), (1, 512, 2)])
+                                      (100, 128, 1), (1, 512, 2),
+                                      (329280, 64, 1), (1317120, 64, 1)])      # trunk.4 and the stem of 105 images of 224 x 224
 def test_bn_stats_apply_backward(rows, C, G):
     x = rnd((G * rows, C), 12) * 2.0 + 3.0            # non-zero mean: exercises the shifted-moment path
     gamma, beta = rnd((C,), 13).abs() + 0.5, rnd((C,), 14)
@@ -236,9 +248,22 @@ def test_bn_stats_apply_backward(rows, C, G):
         out = torch.relu((xa - mu) / torch.sqrt(va + 1e-5) * ga + ba + res.double().view(G, rows, C))
         gx, = torch.autograd.grad(out, xa, dy.double().view(G, rows, C), retain_graph=True)
         dx, dg, db = ops.bn_backward(xg, dy.to(DEV), C, rows, G, mean, rstd, gamma.to(DEV), relu_out=y)
+        # The kernel takes the ReLU decision from the ``relu_out`` it is handed (the fp32 y above), float64 from its own relu().  Among
+        # the 84 M elements of the 1,317,120-row case a few pre-activations lie within fp32 rounding of zero and are decided the other
+        # way (measured: dx off by a whole dy, 0.43, at such an element).  Those elements are counted (at most one in a million:
+        # none is allowed below a million elements, where this is the plain relu() reference), both sides must be within the apply
+        # bar of zero there, and at those elements alone the float64 side differentiates with the kernel's decision.
+        flip = (y.cpu().view(G, rows, C) > 0) != (out.detach() > 0)
+        n_flip = int(flip.sum())
+        assert n_flip <= max(0, flip.numel() // 1000000), n_flip
+        dyd = dy.double().view(G, rows, C)
+        if n_flip:
+            assert float(torch.maximum(y.cpu().double().view(G, rows, C)[flip], out.detach()[flip]).max()) < 2e-5
+            out = out * (~flip) + ((xa - mu) / torch.sqrt(va + 1e-5) * ga + ba + res.double().view(G, rows, C)) * (flip & (y.cpu().view(G, rows, C) > 0))
+            gx, = torch.autograd.grad(out, xa, dyd, retain_graph=True)
         assert float((dx.cpu().double().view(G, rows, C) - gx).abs().max()) < 5e-5 * max(1.0, float(gx.abs().max()))
         for g in range(G):
-            gg, gb = torch.autograd.grad(out[g], [ga, ba], dy.double().view(G, rows, C)[g], retain_graph=True)
+            gg, gb = torch.autograd.grad(out[g], [ga, ba], dyd[g], retain_graph=True)
             assert float((dg[g].cpu().double() - gg).abs().max()) < 1e-4 * max(1.0, float(gg.abs().max()))
             assert float((db[g].cpu().double() - gb).abs().max()) < 1e-4 * max(1.0, float(gb.abs().max()))
 
@@ -336,8 +361,9 @@ def test_bn_apply_residual_bn():
     assert float((y.cpu().double().view(G, rows, C) - ref).abs().max()) < 3e-5
 
 
-def test_stem_tail_and_pools():
-    n, H, C = 10, 42, 64
+@pytest.mark.parametrize("H,PS", [(42, 3), (112, 7)])          # 84 x 84 images (3 x 3 global pool); 224 x 224 (stem side 112, 7 x 7 pool)
+def test_stem_tail_and_pools(H, PS):
+    n, C = 10, 64
     x = rnd((n, C, H, H), 23)
     gamma, beta = rnd((C,), 24).abs() + 0.5, rnd((C,), 25)
     xg = nhwc(x).to(DEV)
@@ -352,13 +378,13 @@ def test_stem_tail_and_pools():
     ref = torch.cat(refs)
     assert float((nchw(y.cpu()).double() - ref).abs().max()) < 2e-5
     # global avgpool + its backward fused with relu backward
-    o = torch.relu(rnd((n, 512, 3, 3), 26))
+    o = torch.relu(rnd((n, 512, PS, PS), 26))
     og = nhwc(o).to(DEV)
     f = ops.global_avgpool(og)
     assert float((f.cpu().double() - o.double().mean((2, 3))).abs().max()) < 1e-6
     df = rnd((n, 512), 27)
     d = ops.avgpool_relu_backward(df.to(DEV), og)
-    ref = (o > 0).double() * df.double()[:, :, None, None] / 9.0
+    ref = (o > 0).double() * df.double()[:, :, None, None] / float(PS * PS)
     assert float((nchw(d.cpu()).double() - ref).abs().max()) < 1e-7
 
 
@@ -781,7 +807,9 @@ def test_fused_block_entry_and_dgrad_bn_backward(ipg, monkeypatch):
 
 
 @pytest.mark.parametrize("name,Cin,Cout,k,stride,pad,H,ipg", [("trunk.4.C1", 64, 64, 3, 1, 1, 21, 5), ("trunk.5.C1", 64, 128, 3, 2, 1, 21, 5),
-                                                             ("trunk.6.C2", 256, 256, 3, 1, 1, 6, 5), ("trunk.5.sc", 64, 128, 1, 2, 0, 21, 3)])
+                                                             ("trunk.6.C2", 256, 256, 3, 1, 1, 6, 5), ("trunk.5.sc", 64, 128, 1, 2, 0, 21, 3),
+                                                             ("trunk.4.C1@224", 64, 64, 3, 1, 1, 56, 5), ("trunk.5.C1@224", 64, 128, 3, 2, 1, 56, 5),
+                                                             ("trunk.6.C1@224", 128, 256, 3, 2, 1, 28, 5), ("trunk.6.C2@224", 256, 256, 3, 1, 1, 14, 5)])
 def test_conv_x3_fused_bn_statistics(name, Cin, Cout, k, stride, pad, H, ipg):
     """BatchNorm statistics produced in the bf16x3 convolution epilogue (tiles straddling group boundaries, ragged last tile,
     Chan merge) against float64 statistics of the convolution output, and the same convolution output as the plain launch."""
@@ -1097,7 +1125,8 @@ def test_wgrad_adam_next_forward_xcd_order_is_bit_identical(G):
     assert not torch.equal(outs[0][0], w0)
 
 
-@pytest.mark.parametrize("Cin,Cout,H,ipg,G", [(64, 64, 21, 5, 6), (128, 128, 11, 5, 7), (64, 128, 11, 3, 5), (256, 256, 6, 5, 4)])
+@pytest.mark.parametrize("Cin,Cout,H,ipg,G", [(64, 64, 21, 5, 6), (128, 128, 11, 5, 7), (64, 128, 11, 3, 5), (256, 256, 6, 5, 4),
+                                              (64, 64, 56, 5, 3), (128, 128, 28, 5, 4), (256, 256, 14, 5, 4)])       # 224 x 224 sides
 def test_conv_x3_loader_side_batchnorm_is_bit_identical(Cin, Cout, H, ipg, G):
     """SimpleBlock's C1 -> BN1 -> ReLU -> C2 (backbone.py:251-256) with BN1 folded into C2's loader
     (mft_conv2d_nhwc_x3_bnin_bnstats: statistics merged from C1's partials in the workgroup prologue) against the separate
@@ -1134,11 +1163,23 @@ def test_conv_x3_loader_side_batchnorm_is_bit_identical(Cin, Cout, H, ipg, G):
     # (256 channels on 6x6 maps were refused while the staged image carried a zero row per image-row boundary: 152 rows; with one
     #  zero row -- 131 rows -- the (scale, shift) table fits beside the tile at three workgroups per CU.)  The stand-alone apply
     #  from partials that a refusing shape falls back to is checked against the plain apply either way:
-    r1b = ops.bn_apply_x3ws(c1b.view(-1, Cin), Cin, rows, G, ws1b, g1, b1, torch.empty((n * H * H, Cin), device=DEV), act=ops.ACT_RELU)
-    assert torch.equal(r1b.view_as(r1), r1)
-    assert r is not None
-    assert torch.equal(out, ref)
-    assert torch.equal(m2b, m2) and torch.equal(s2b, s2)
+    if lib.mft_bn_apply_x3ws_fits(Cin, rows, 0):
+        r1b = ops.bn_apply_x3ws(c1b.view(-1, Cin), Cin, rows, G, ws1b, g1, b1, torch.empty((n * H * H, Cin), device=DEV), act=ops.ACT_RELU)
+        assert torch.equal(r1b.view_as(r1), r1)
+    else:       # 5 images of 56 x 56 / 28 x 28: the partials of so long a group do not fit the apply's LDS stage either -- refused
+        assert H in (56, 28)
+        with pytest.raises(RuntimeError, match="-22"):
+            ops.bn_apply_x3ws(c1b.view(-1, Cin), Cin, rows, G, ws1b, g1, b1, torch.empty((n * H * H, Cin), device=DEV), act=ops.ACT_RELU)
+    if H in (56, 28, 14):
+        # the groups of a 224 x 224 image (15,680 / 3,920 / 980 rows) are outside the fused form's domain: the merge stage of so many
+        # tile partials does not fit beside the tile.  It must REFUSE and write nothing; what the caller then runs -- finalize, apply,
+        # plain convolution: ``ref`` above -- is held to float64 below
+        assert r is None and not bool(out.any())
+        out = ref
+    else:
+        assert r is not None
+        assert torch.equal(out, ref)
+        assert torch.equal(m2b, m2) and torch.equal(s2b, s2)
     # against float64: relu(BN(c1)) convolved in double
     c1d = c1.double().cpu().view(G, rows, Cin)
     mu, var = c1d.mean(1, keepdim=True), c1d.var(1, unbiased=False, keepdim=True)
@@ -1156,7 +1197,8 @@ def test_conv_x3_loader_side_batchnorm_is_bit_identical(Cin, Cout, H, ipg, G):
                                           torch.empty(int(lib.mft_conv2d_x3_stats_ws_floats(8, 6, 6, 64, 3, 3, 1, 1)), device=DEV)) is None
 
 
-@pytest.mark.parametrize("C,H,ipg,G,res", [(64, 21, 5, 6, "identity"), (128, 11, 5, 7, "bn"), (256, 6, 5, 5, "bn"), (64, 21, 3, 4, "none")])
+@pytest.mark.parametrize("C,H,ipg,G,res", [(64, 21, 5, 6, "identity"), (128, 11, 5, 7, "bn"), (256, 6, 5, 5, "bn"), (64, 21, 3, 4, "none"),
+                                           (64, 56, 5, 3, "identity"), (128, 28, 5, 4, "bn"), (256, 14, 5, 4, "bn")])          # 224 x 224 sides
 def test_bn_apply_from_partials_is_bit_identical(C, H, ipg, G, res):
     """mft_bn_apply_x3ws (statistics of the main and the residual BatchNorm merged from convolution partials inside the apply
     launch) against finalize + finalize + mft_bn_apply: output and merged statistics bit for bit."""
@@ -1188,6 +1230,13 @@ def test_bn_apply_from_partials_is_bit_identical(C, H, ipg, G, res):
         kw_ref = kw_new = dict(res=x.view(-1, 64))
     ref = ops.bn_apply(c2.view(-1, C), C, rows, G, m2, s2, g2, b2, act=ops.ACT_RELU, fma_affine=True, **kw_ref)
     mo, so = torch.empty((G, C), device=DEV), torch.empty((G, C), device=DEV)
+    if not lib.mft_bn_apply_x3ws_fits(C, rows, 1 if res == "bn" else 0):
+        # 5 images of 56 x 56 / 28 x 28 per group: the partials of so long a group do not fit the launch's LDS stage.  The form must
+        # REFUSE (the caller then runs finalize + mft_bn_apply: the ``ref`` above), never compute something else
+        assert H in (56, 28)
+        with pytest.raises(RuntimeError, match="-22"):
+            ops.bn_apply_x3ws(c2.view(-1, C), C, rows, G, ws2, g2, b2, torch.empty_like(ref), act=ops.ACT_RELU, stats=(mo, so), **kw_new)
+        return
     out = ops.bn_apply_x3ws(c2.view(-1, C), C, rows, G, ws2, g2, b2, torch.empty_like(ref), act=ops.ACT_RELU, stats=(mo, so), **kw_new)
     assert torch.equal(out, ref)
     assert torch.equal(mo, m2) and torch.equal(so, s2)
@@ -1336,7 +1385,7 @@ def test_stem_wgrad_strip_kernel(n, H):
     assert float((got - gen).abs().max()) < 3e-5 * sc
 
 
-@pytest.mark.parametrize("n,H,C", [(5, 42, 64), (3, 13, 32), (2, 8, 6)])
+@pytest.mark.parametrize("n,H,C", [(5, 42, 64), (3, 13, 32), (2, 8, 6), (5, 112, 64)])
 def test_maxpool_relu_backward_matches_autograd(n, H, C):
     """BatchNorm -> ReLU -> MaxPool2d(3, 2, 1) of the stem (backbone.py:295-297) with the argmax recorded, and its gradient w.r.t.
     the BatchNorm output (four channels per thread where C % 4 == 0, scalar otherwise) against torch autograd."""
@@ -1547,7 +1596,8 @@ def test_conv_wgrad_multi_is_bit_identical_to_single_launches():
     assert torch.equal(off.add(x, dy, 64, 3, 3, 1, 1), ops.conv2d_wgrad_oihw(x, dy, 64, 3, 3, 1, 1))
 
 
-@pytest.mark.parametrize("rows,C,groups", [(945, 512, 1), (3780, 256, 1), (12705, 128, 1), (4 * 945, 512, 4), (46305, 64, 1)])
+@pytest.mark.parametrize("rows,C,groups", [(945, 512, 1), (3780, 256, 1), (12705, 128, 1), (4 * 945, 512, 4), (46305, 64, 1),
+                                           (82320, 128, 1), (20580, 256, 1)])       # trunk.5 / trunk.6 of 105 images of 224 x 224
 def test_bn_stats_and_backward_multi_are_bit_identical_to_single_launches(rows, C, groups):
     """mft_bn_stats_multi / mft_bn_backward_act_multi (SimpleBlock's BN2 + BNshortcut as one launch pair / triple in the meta-training
     step) against the same problems launched one by one: mean, rstd, running statistics and counter, dx, dgamma, dbeta bit for bit."""

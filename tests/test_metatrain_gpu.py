@@ -126,14 +126,16 @@ def test_split_precision_training_layers_match_the_fp32_launches(monkeypatch):
     assert worst[0][1] < 3e-2 and worst[0][2] < 6e-3 and worst[1][1] < 1e-1 and worst[1][2] < 4e-2, worst
 
 
-def test_train_loop2_step_matches_oracle():
-    """One optimizer step of train.py's loop: zero_grad, set_forward_loss, backward, Adam step (train.py:28)."""
+@pytest.mark.parametrize("size", [84, 224])
+def test_train_loop2_step_matches_oracle(size):
+    """One optimizer step of train.py's loop: zero_grad, set_forward_loss, backward, Adam step (train.py:28); at 84 x 84 and at the
+    reference's 224 x 224 (there also trunk.6.C2, on the split-precision kernels at that size, and the stem)."""
     sd = synthetic.gnnnet_state_dict(seed=27)
     model = GnnNet(model_dict['ResNet10'], n_way=5, n_support=5)
     model.load_state_dict(sd)
     model = model.cuda()
     opt = torch.optim.Adam(model.parameters())
-    x = synthetic.train_episode(61, 5, 5, 16, 84)
+    x = synthetic.train_episode(61, 5, 5, 16, size)
 
     class OneEpisode:
         def __len__(self):
@@ -146,7 +148,10 @@ def test_train_loop2_step_matches_oracle():
     ref_loss, _, ref = _oracle_grads(sd, x)
     # first Adam step moves every weight by lr*sign(g): check on the well-conditioned entries
     named = dict(model.named_parameters())
-    for k in ("fc.0.weight", "gnn.layer_last.fc.weight", "feature.trunk.7.C2.weight", "feature.trunk.4.C1.weight"):
+    keys = ("fc.0.weight", "gnn.layer_last.fc.weight", "feature.trunk.7.C2.weight", "feature.trunk.4.C1.weight")
+    if size == 224:
+        keys += ("feature.trunk.6.C2.weight", "feature.trunk.0.weight")
+    for k in keys:
         gr = ref[k]
         big = gr.abs() > 1e-2 * float(gr.abs().max())
         delta = (named[k].detach().cpu().double() - sd[k].double())[big]
@@ -486,16 +491,16 @@ def test_one_launch_repack_after_in_place_update():
     assert AG.module_weights(model2.feature) is not W0
 
 
-@pytest.mark.parametrize("variant", ["gnnnet", "gnnnet_copy", "gnnnet_20way"])
+@pytest.mark.parametrize("variant", ["gnnnet", "gnnnet_copy", "gnnnet_20way", "gnnnet_224"])
 def test_graphed_episode_loop_is_bit_identical(variant, capsys, monkeypatch):
     """MetaTemplate's episode loop (meta_template.py:76-92) with forward + backward replayed from ONE hipGraph after three eager
     steps (graph_step.GraphedLossBackward) against the plain loop: the printed loss lines and every parameter after 9 steps
     with the fused outer Adam must match bit for bit -- also after the loader changes the episode's shape (recapture) and when
-    the optimizer runs between replays.  ``gnnnet_20way``: 20-way 5-shot at train.py's 4 queries (then 3)."""
+    the optimizer runs between replays.  ``gnnnet_20way``: 20-way 5-shot at train.py's 4 queries (then 3); ``gnnnet_224``: 224 x 224 images."""
     from meta_fine_tuning_amd import graph_step, optim
     from meta_fine_tuning_amd.methods import gnnnet_copy
     cls, n_way, n_shot, size, nq = {"gnnnet": (GnnNet, 5, 5, 84, (16, 12)), "gnnnet_copy": (gnnnet_copy.GnnNet, 5, 50, 42, (16, 12)),
-                                    "gnnnet_20way": (GnnNet, 20, 5, 84, (4, 3))}[variant]
+                                    "gnnnet_20way": (GnnNet, 20, 5, 84, (4, 3)), "gnnnet_224": (GnnNet, 5, 5, 224, (16, 12))}[variant]
     eps = [synthetic.train_episode(700 + i, n_way, n_shot, nq[0], size) for i in range(5)]       # host tensors, as a DataLoader yields
     eps += [synthetic.train_episode(710 + i, n_way, n_shot, nq[1], size) for i in range(4)]      # the loader switches to fewer queries
 

@@ -124,6 +124,44 @@ def test_g21_episode_shapes(golden_dir, n_way, n_shot, n_query, wseed, xseed):
     np.testing.assert_allclose(gd["gnn.layer_last.fc.bias"].numpy(), g["grad_lastb_" + t], atol=1e-6)
 
 
+G23_CASES = [(224, 7, 21), (100, 8, 22)]     # = oracle/make_golden_g23.py CASES (image size, weight seed, episode seed)
+
+
+@pytest.mark.parametrize("size,wseed,xseed", G23_CASES)
+def test_g23_image_sizes(golden_dir, size, wseed, xseed):
+    """The oracle's meta-training step in fp32 against the reference's fp32 GnnNet.set_forward_loss + backward at 224 x 224 (the
+    reference's native size, its own AvgPool2d(7)) and at 100 x 100 (G23): pins the oracle at the image sizes the GPU tests of
+    tests/test_image_sizes_gpu.py compare against.  Same bars as G21; the slices of the trunk gradients as G3."""
+    g = _g(golden_dir, "g23_image_sizes.npz")
+    assert [tuple(r) for r in g["cases"].tolist()] == G23_CASES
+    t = str(size)
+    dt = torch.float32
+    sd = O.clone_state(synthetic.gnnnet_state_dict(seed=wseed), dt)
+    x = synthetic.train_episode(xseed, 5, 5, 16, size).to(dt)
+    pkeys = [k for k, v in sd.items() if v.is_floating_point() and "running" not in k]
+    for k in pkeys:
+        sd[k].requires_grad_(True)
+    loss, scores = O.meta_train_loss(sd, x, 5, 5)
+    assert scores.shape == (80, 5)
+    np.testing.assert_allclose(scores.detach().numpy(), g["scores_" + t], atol=2e-5)
+    assert abs(float(loss.detach()) - float(g["loss_" + t])) < 1e-5
+    grads = torch.autograd.grad(loss, [sd[k] for k in pkeys])
+    gn = {k: float(v.norm()) for k, v in zip(pkeys, grads)}
+    assert sorted(gn) == [str(n) for n in g["gradnames_" + t]]
+    for name, ref in zip(g["gradnames_" + t], g["gradnorms_" + t]):
+        if ref < 1e-5:                          # a bias in front of a BatchNorm: zero in exact arithmetic, rounding noise in fp32
+            assert gn[str(name)] < 1e-5, name
+            continue
+        assert abs(gn[str(name)] - ref) <= 1e-3 * ref + 1e-7, name
+    gd = dict(zip(pkeys, grads))
+    np.testing.assert_allclose(gd["fc.0.weight"][:4, :8].numpy(), g["grad_fc0w_slice_" + t], atol=1e-5)
+    for key, sl, name in (("feature.trunk.7.C2.weight", (slice(0, 2), slice(0, 4), 1, 1), "grad_c7c2_slice_"),
+                          ("feature.trunk.6.C2.weight", (slice(0, 4), slice(0, 8)), "grad_c6c2_slice_"),
+                          ("feature.trunk.0.weight", (slice(0, 2), slice(None), 3, 3), "grad_stem_slice_")):
+        want = g[name + t]
+        np.testing.assert_allclose(gd[key][sl].numpy(), want, atol=max(1e-5, 1e-3 * float(np.abs(want).max())), err_msg=key)
+
+
 @pytest.mark.parametrize("tag,dt", [("f32", torch.float32), ("f64", torch.float64)])
 def test_g4_inner_loop(golden_dir, tag, dt):
     g = _g(golden_dir, "g4_inner_loop.npz")
