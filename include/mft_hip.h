@@ -463,6 +463,36 @@ int mft_proto_scores(const float* feats, int ld, int episodes, int n_way, int n_
 int mft_proto_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
                        const float* dscores, int ldg, float* dfeats, int ldd, void* stream);
 
+/* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
+ * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
+ *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)
+ * forward: ONE launch that also computes the row norms of x and V; rows [grp * rows_per_group, (grp + 1) * rows_per_group) of x
+ * are scored with group grp's V and g (n_groups = 1: the training head; n_groups = E: the queries of E adapted episodes);
+ * scores [n_groups * rows_per_group, C] contiguous; softmax = 1: their row softmax instead.
+ * backward (one group), G = dscores (row stride ldg >= C), u[r,c] = (xh_r . v_c) / ||v_c||, ONE launch of row-role and class-role
+ * workgroups that writes every element of its outputs once (no atomics, no zero fill, fixed summation order):
+ *   dg_c = s sum_r G[r,c] u[r,c];   dV_c = s g_c / ||v_c|| (sum_r G[r,c] xh_r - (sum_r G[r,c] u[r,c]) v_c / ||v_c||)
+ *   dx_r = dxh_r / (n_r + eps) - x_r (dxh_r . x_r) / (n_r (n_r + eps)^2),  dxh_r = s sum_c G[r,c] g_c v_c / ||v_c||
+ * (second term 0 for a zero row); dx (row stride ldd) may be NULL: the row-role workgroups are then not launched.
+ * MFT_EINVAL outside C 1..1024, D <= 512 a multiple of 4, leading dimensions >= D and multiples of 4, rows >= 1, groups >= 1,
+ * 16-byte aligned x / V / dx / dV. */
+int mft_dist_linear_forward(const float* x, int ldx, int n_groups, int rows_per_group, const float* V, const float* g, int C,
+                            int D, float s, float* scores, int softmax, void* stream);
+int mft_dist_linear_backward(const float* x, int ldx, int rows, const float* V, const float* g, int C, int D, float s,
+                             const float* dscores, int ldg, float* dx, int ldd, float* dV, float* dg, void* stream);
+
+/* BaselineFinetune(loss_type='dist').set_forward_adaptation (baselinefinetune.py:17-58) as ONE launch, the distLinear counterpart
+ * of mft_linear_head_sgd_run with the same index-table contract: per group (episode) a head V [n_groups, n_way, D],
+ * g [n_groups, n_way] (both updated in place) is trained on the frozen support features z_support [n_groups, n_support_rows, D]
+ * with torch.optim.SGD(lr, momentum, dampening, L2 weight_decay on g and V; first step: momentum buffer = gradient) for n_steps
+ * mini-batches, loss = mean cross entropy of the mini-batch's scores (scale s); idx_table [n_groups, n_steps, batch_size] holds
+ * the support row of every mini-batch slot (-1 = empty slot of a ragged batch), y_support [n_groups, n_support_rows] the labels.
+ * One workgroup per group; the support rows sit in LDS when they fit beside V and its momentum, else they are read from HBM / L2.
+ * MFT_EINVAL outside n_way 1..16, batch_size 1..16, D <= 512 a multiple of 4, n_steps / n_groups / n_support_rows >= 1. */
+int mft_dist_head_sgd_run(const float* z_support, const int* y_support, const int* idx_table, int n_groups, int n_support_rows,
+                          int D, int n_way, int n_steps, int batch_size, float* V, float* g, float s, float lr, float momentum,
+                          float dampening, float weight_decay, void* stream);
+
 /* optimisers --------------------------------------------------------------------------- */
 /* torch.optim.Adam.step (finetune.py:255,299; gnnnet.py:128,177; train.py:28), one flat slab of n floats:
  * g += wd*p; m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g*g; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps) */

@@ -358,3 +358,33 @@ def protonet_head(feats, n_way, n_support, n_query, episodes=1):
     if torch.is_grad_enabled() and feats.requires_grad:
         return _ProtoHeadFn.apply(feats, n_way, n_support, n_query, episodes)
     return ops.proto_scores(feats.detach(), episodes, n_way, n_support, n_query)
+
+
+class _DistLinearFn(torch.autograd.Function):
+    """Baseline++ head (backbone.distLinear): one mft_dist_linear_forward launch forward, one mft_dist_linear_backward launch
+    back for dx, dg and dv together."""
+
+    @staticmethod
+    def forward(ctx, x, g, v, scale):
+        ctx.save_for_backward(x, g, v)
+        ctx.scale = scale
+        return ops.dist_linear_forward(x, g, v, scale)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        x, g, v = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.stride(1) == 1) else dscores.contiguous().float()
+        dx, dv, dg = ops.dist_linear_backward(x, g, v, ctx.scale, d, need_dx=ctx.needs_input_grad[0])
+        return dx, dg, dv, None
+
+
+def dist_linear(x, g, v, scale):
+    """backbone.distLinear.forward: x [R, D], g [C, 1], v [C, D] -> scale * cosine scores [R, C].  Differentiable in x, g and v
+    when autograd records."""
+    _require_cuda(x, "distLinear")
+    _require_cuda(v, "distLinear")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        x = x.contiguous().float()
+    if torch.is_grad_enabled() and (x.requires_grad or g.requires_grad or v.requires_grad):
+        return _DistLinearFn.apply(x, g.contiguous(), v.contiguous(), float(scale))
+    return ops.dist_linear_forward(x.detach(), g.detach().contiguous(), v.detach().contiguous(), float(scale))

@@ -100,3 +100,35 @@ class ResNet(nn.Module):
 
 def ResNet10(flatten=True):
     return ResNet(SimpleBlock, [1, 1, 1, 1], [64, 128, 256, 512], flatten)
+
+
+class _WeightNormLinear(nn.Module):
+    """Parameter container with the keys, shapes and registration order of
+    ``WeightNorm.apply(nn.Linear(indim, outdim, bias=False), 'weight', dim=0)``: ``weight_g`` [outdim, 1], ``weight_v``
+    [outdim, indim].  No hook recomposes a ``weight``: the head kernels read g and v directly."""
+
+    def __init__(self, indim, outdim):
+        super().__init__()
+        self.in_features, self.out_features = indim, outdim
+        v = nn.Linear(indim, outdim, bias=False).weight.data        # the draw the torch class makes from the global RNG
+        self.weight_g = nn.Parameter(torch.norm_except_dim(v, 2, 0).data)
+        self.weight_v = nn.Parameter(v)
+
+    def forward(self, x):
+        raise RuntimeError("distLinear.L is executed by distLinear.forward on the HIP path, not on its own")
+
+
+class distLinear(nn.Module):
+    """Baseline++ cosine classifier ("A Closer Look at Few-shot Classification"): scores = scale_factor * cos-similarity of
+    x / (||x|| + 1e-5) and the weight-normalised rows g_c v_c / ||v_c||, scale_factor 2 up to 200 classes and 10 above, no bias.
+    The state dict is the torch weight-norm module's (``L.weight_g``, ``L.weight_v``); forward and backward are one HIP launch
+    each (autograd_ops.dist_linear)."""
+
+    def __init__(self, indim, outdim):
+        super().__init__()
+        self.L = _WeightNormLinear(indim, outdim)
+        self.class_wise_learnable_norm = True
+        self.scale_factor = 2 if outdim <= 200 else 10
+
+    def forward(self, x):
+        return AG.dist_linear(x, self.L.weight_g, self.L.weight_v, self.scale_factor)

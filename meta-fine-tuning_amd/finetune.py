@@ -331,6 +331,49 @@ def finetune_linear_batched(episodes, state_in, n_way=5, n_support=5, episodes_p
     return torch.cat(out)
 
 
+BASELINEPP_EPOCHS = 100     # baselinefinetune.py:42
+
+
+def dist_head_init(n_way, dim=512, n=1):
+    """Initial (v0 [n, n_way, dim], g0 [n, n_way, 1]) of ``n`` fresh backbone.distLinear(dim, n_way) heads: one draw per episode
+    from torch's global RNG, in episode order, as BaselineFinetune(loss_type='dist') makes them."""
+    from . import backbone
+    heads = [backbone.distLinear(dim, n_way) for _ in range(n)]
+    return torch.stack([h.L.weight_v.data for h in heads]), torch.stack([h.L.weight_g.data for h in heads])
+
+
+def baselinepp_batched(episodes, state_in, n_way=5, n_support=5, episodes_per_batch=32, perms=None, heads=None):
+    """Baseline++ adaptation (BaselineFinetune(loss_type='dist').set_forward on the checkpoint's eval-mode features of view 0)
+    over a list of episodes, ``episodes_per_batch`` heads per launch: features through ``_eval_backbone``, then per batch ONE
+    mft_dist_head_sgd_run launch (100 epochs of mini-batches of 4 for every head) and ONE scoring launch with its softmax
+    epilogue.  ``perms[i]``: the 100 permutations of episode i (default: drawn episode by episode from the global numpy RNG);
+    ``heads`` = (v0 [n, n_way, 512], g0 [n, n_way, 1]) (default: ``dist_head_init``).  -> [n * n_way * n_query, n_way]."""
+    from .methods.meta_template import dist_head_adapt
+    n = len(episodes)
+    x0 = episodes[0][0]
+    n_query = x0.size(1) - n_support
+    S = n_way * n_support
+    if perms is None:
+        perms = [[np.random.permutation(S) for _ in range(BASELINEPP_EPOCHS)] for _ in range(n)]
+    v0, g0 = dist_head_init(n_way, n=n) if heads is None else (torch.as_tensor(heads[0]), torch.as_tensor(heads[1]))
+    feat = _eval_backbone(state_in, params.model if params is not None else 'ResNet10')
+    y_support = np.repeat(np.arange(n_way), n_support)
+    out = []
+    for i in range(0, n, episodes_per_batch):
+        chunk = episodes[i:i + episodes_per_batch]
+        zs, zq = [], []
+        with torch.no_grad():
+            for liz_x in chunk:
+                x = liz_x[0].cuda()
+                z = feat(x.reshape(-1, *x.shape[2:])).float().view(n_way, n_support + n_query, -1)
+                zs.append(z[:, :n_support].reshape(S, -1))
+                zq.append(z[:, n_support:].reshape(n_way * n_query, -1))
+        sc, _, _ = dist_head_adapt(torch.stack(zs), y_support, torch.stack(zq), v0[i:i + len(chunk)], g0[i:i + len(chunk)], n_way,
+                                   n_support, epochs=BASELINEPP_EPOCHS, perms=perms[i:i + len(chunk)], softmax=True)
+        out.append(sc)
+    return torch.cat(out)
+
+
 def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch, n_way=5, n_support=5, episodes_per_batch=32,
                    rngs=None, classifiers=None, parts=False):
     """What the reference's loop body computes for each episode of ``episodes`` (finetune.py:615-619,647-649), in lockstep:

@@ -16,7 +16,7 @@ _COMMON = [
     ("--test_dataset", dict(default="", help="test dataset")),
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
-    ("--method", dict(default="baseline", help="baseline/protonet/gnnnet/all")),
+    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/gnnnet/all")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),
     ("--test_n_way", dict(default=5, type=int, help="class num to classify for testing (validation)")),
     ("--n_shot", dict(default=5, type=int, help="number of labeled data in each class, same as n_support")),
@@ -31,7 +31,7 @@ _COMMON = [
 _PER_SCRIPT = {
     "train": [
         ("--fine_tune", dict(action="store_true", help="fine tuning during training")),
-        ("--num_classes", dict(default=200, type=int, help="total number of classes in softmax (baseline only)")),
+        ("--num_classes", dict(default=200, type=int, help="total number of classes in softmax (baseline / baseline++ only)")),
         ("--save_freq", dict(default=50, type=int, help="Save frequency")),
         ("--start_epoch", dict(default=0, type=int, help="Starting epoch")),
         ("--stop_epoch", dict(default=400, type=int, help="Stopping epoch")),

@@ -1,11 +1,13 @@
 """Supervised pre-training of the "baseline" checkpoint of the README ensemble (mirror of methods/baselinetrain.py:10-59):
 backbone features -> nn.Linear(512, num_class) -> cross entropy, ordinary mini-batches.  The backbone runs through the
 HIP forward / full backward (autograd_ops), the classifier through the same GEMM / weight-gradient kernels
-(functional_bwd._linear_fwd/_linear_bwd); `loss_type='dist'` (Baseline++, backbone.distLinear) is outside the hot path."""
+(functional_bwd._linear_fwd/_linear_bwd); `loss_type='dist'` (Baseline++) swaps the classifier for backbone.distLinear, one
+launch each way (mft_dist_linear_forward / mft_dist_linear_backward)."""
 import torch
 import torch.nn as nn
 
 from .. import autograd_ops as AG
+from .. import backbone
 from .. import functional_bwd as FB
 from .. import ops
 
@@ -52,11 +54,14 @@ class AverageMeter(object):
 class BaselineTrain(nn.Module):
     def __init__(self, model_func, num_class, loss_type='softmax'):
         super(BaselineTrain, self).__init__()
-        if loss_type != 'softmax':
-            raise NotImplementedError("loss_type='dist' (Baseline++) is outside the HIP hot path")
+        if loss_type not in ('softmax', 'dist'):
+            raise ValueError("loss_type must be 'softmax' or 'dist', got %r" % (loss_type,))
         self.feature = model_func()
-        self.classifier = nn.Linear(self.feature.final_feat_dim, num_class)
-        self.classifier.bias.data.fill_(0)                               # baselinetrain.py:17
+        if loss_type == 'softmax':
+            self.classifier = nn.Linear(self.feature.final_feat_dim, num_class)
+            self.classifier.bias.data.fill_(0)                           # baselinetrain.py:17
+        else:                                                            # Baseline++ (baselinetrain.py:18-19)
+            self.classifier = backbone.distLinear(self.feature.final_feat_dim, num_class)
         self.loss_type = loss_type
         self.num_class = num_class
         self.loss_fn = AG.CrossEntropyLoss()                             # nn.CrossEntropyLoss() (baselinetrain.py:20), HIP launches
@@ -64,6 +69,8 @@ class BaselineTrain(nn.Module):
 
     def forward(self, x):
         out = self.feature.forward(x.cuda())
+        if self.loss_type == 'dist':
+            return self.classifier(out)
         return _LinearFn.apply(out, self.classifier.weight, self.classifier.bias)
 
     def forward_loss(self, x, y):

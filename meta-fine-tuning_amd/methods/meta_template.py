@@ -183,6 +183,44 @@ def linear_head_adapt(z_support, y_support, z_query, w, b, n_way, n_support, epo
     return ops.gemm(z_query, K, wpad[:n_way].contiguous(), n_way, bias=bias[0].contiguous())
 
 
+def adaptation_table(support_size, epochs, batch_size, perms=None):
+    """Index table [epochs * ceil(support_size / batch_size), batch_size] of the head-adaptation loop (baselinefinetune.py:42-46):
+    one permutation of the support rows per epoch -- drawn from the global numpy stream unless ``perms`` gives them -- cut into
+    mini-batches, the ragged last one padded with -1."""
+    steps = []
+    for epoch in range(epochs):
+        rand_id = np.random.permutation(support_size) if perms is None else np.asarray(perms[epoch])
+        if rand_id.shape != (support_size,) or rand_id.min() < 0 or rand_id.max() >= support_size:
+            raise ValueError("adaptation_table: epoch %d is not a permutation of %d support rows" % (epoch, support_size))
+        for i in range(0, support_size, batch_size):
+            ids = rand_id[i:min(i + batch_size, support_size)]
+            steps.append(np.concatenate([ids, -np.ones(batch_size - len(ids), dtype=ids.dtype)]))
+    return np.stack(steps).astype(np.int32)
+
+
+def dist_head_adapt(z_support, y_support, z_query, v0, g0, n_way, n_support, epochs=100, batch_size=4, perms=None, softmax=False):
+    """BaselineFinetune(loss_type='dist').set_forward_adaptation (baselinefinetune.py:17-58) for E episodes at once:
+    z_support [E, S, D], y_support [S] or [E, S], z_query [E, Q, D], v0 [E, n_way, D], g0 [E, n_way(, 1)] (not modified).
+    The permutations of all epochs are drawn first, episode by episode (``perms[e][epoch]`` pins them), then ONE
+    mft_dist_head_sgd_run launch trains the E heads with SGD(0.01, 0.9, 0.9, 0.001) and ONE mft_dist_linear_forward launch scores
+    every episode's queries with its own head.  -> (raw scores [E * Q, n_way] -- ``softmax``: their row softmax, from the same
+    launch --, v [E, n_way, D], g [E, n_way])."""
+    dev = z_support.device
+    E, S, D = z_support.shape
+    if S != n_way * n_support:
+        raise ValueError("dist_head_adapt: %d support rows are not n_way * n_support = %d" % (S, n_way * n_support))
+    table = np.stack([adaptation_table(S, epochs, batch_size, None if perms is None else perms[e]) for e in range(E)])
+    y = np.broadcast_to(np.asarray(y_support).astype(np.int32).reshape(-1, S), (E, S))
+    table = torch.from_numpy(table).to(dev)
+    y_dev = torch.from_numpy(np.ascontiguousarray(y)).to(dev)
+    v = v0.detach().to(dev, torch.float32).reshape(E, n_way, D).clone()
+    g = g0.detach().to(dev, torch.float32).reshape(E, n_way).clone()
+    scale = ops.dist_scale(n_way)
+    ops.dist_head_sgd_run(z_support.contiguous().float(), y_dev, table, v, g, scale, 0.01, 0.9, 0.9, 0.001)
+    zq = z_query.contiguous().float().view(-1, D)
+    return ops.dist_linear_forward(zq, g, v, scale, softmax=softmax), v, g
+
+
 def small_tn(a, b):
     """a [k, m], b [k, n] -> a^T b [m, n] through the MFMA GEMM (k padded to 32 with zero rows)."""
     k, m = a.shape

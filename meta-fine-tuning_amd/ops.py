@@ -883,6 +883,74 @@ def proto_backward(feats, dscores, episodes, n_way, n_support, n_query, out=None
     return dx
 
 
+def dist_scale(n_classes):
+    """distLinear's scale factor: 2 up to 200 classes, 10 above."""
+    return 2.0 if n_classes <= 200 else 10.0
+
+
+def _dist_rows(x, what):
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise RuntimeError("%s: expected float32 rows [R, D] with unit column stride, got %s %s" % (what, x.dtype, tuple(x.shape)))
+    return x
+
+
+def dist_linear_forward(x, g, v, scale, softmax=False):
+    """Baseline++ scores (backbone.distLinear), one launch: x [n_groups * rows, D] (row stride free), v [C, D] or
+    [n_groups, C, D], g [C, 1] / [C] or [n_groups, C] -> scale * g_c (x_r . v_c) / ((||x_r|| + 1e-5) ||v_c||) as
+    [n_groups * rows, C]; ``softmax``: the row softmax of that instead."""
+    _dist_rows(x, "dist_linear_forward")
+    _f32c(v)
+    _f32c(g)
+    n_groups = v.shape[0] if v.dim() == 3 else 1
+    C, D = v.shape[-2], v.shape[-1]
+    if n_groups < 1 or g.numel() != n_groups * C or x.shape[1] != D or x.shape[0] % n_groups:
+        raise ValueError("dist_linear_forward: x %s, g %s, v %s do not fit" % (tuple(x.shape), tuple(g.shape), tuple(v.shape)))
+    y = torch.empty((x.shape[0], C), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mft_dist_linear_forward(_p(x), x.stride(0), n_groups, x.shape[0] // n_groups, _p(v), _p(g), C, D,
+                                                  float(scale), _p(y), 1 if softmax else 0, _stream()), "mft_dist_linear_forward")
+    return y
+
+
+def dist_linear_backward(x, g, v, scale, dscores, need_dx=True):
+    """d(scores) [R, C] -> (dx [R, D] | None, dv [C, D], dg shaped like g) of dist_linear_forward with one group: one launch,
+    every output element written once (torch.empty outputs), fixed summation order."""
+    _dist_rows(x, "dist_linear_backward")
+    _dist_rows(dscores, "dist_linear_backward")
+    _f32c(v)
+    _f32c(g)
+    C, D = v.shape
+    if g.numel() != C or x.shape[1] != D or tuple(dscores.shape) != (x.shape[0], C):
+        raise ValueError("dist_linear_backward: x %s, g %s, v %s, dscores %s do not fit"
+                         % (tuple(x.shape), tuple(g.shape), tuple(v.shape), tuple(dscores.shape)))
+    dx = torch.empty((x.shape[0], D), device=x.device, dtype=torch.float32) if need_dx else None
+    dv = torch.empty_like(v)
+    dg = torch.empty_like(g)
+    _lib.check(_lib.lib().mft_dist_linear_backward(_p(x), x.stride(0), x.shape[0], _p(v), _p(g), C, D, float(scale), _p(dscores),
+                                                   dscores.stride(0), _p(dx), D, _p(dv), _p(dg), _stream()),
+               "mft_dist_linear_backward")
+    return dx, dv, dg
+
+
+def dist_head_sgd_run(z_support, y_support, table, v, g, scale, lr=0.01, momentum=0.9, dampening=0.9, weight_decay=0.001):
+    """BaselineFinetune(loss_type='dist') head training, every step of every group in one launch: z_support [G, S, D],
+    y_support [G, S] int32, table [G, T, batch] int32 (support row per mini-batch slot, -1 = empty), v [G, n_way, D] and
+    g [G, n_way] updated IN PLACE with torch.optim.SGD semantics."""
+    for t in (z_support, v, g):
+        _f32c(t)
+    for t in (y_support, table):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError("dist_head_sgd_run: labels and index table must be contiguous int32 tensors")
+    G, S, D = z_support.shape
+    n_way = v.shape[1]
+    if tuple(v.shape) != (G, n_way, D) or g.numel() != G * n_way or tuple(y_support.shape) != (G, S) or table.dim() != 3 \
+            or table.shape[0] != G:
+        raise ValueError("dist_head_sgd_run: z %s, y %s, table %s, v %s, g %s do not fit"
+                         % (tuple(z_support.shape), tuple(y_support.shape), tuple(table.shape), tuple(v.shape), tuple(g.shape)))
+    _lib.check(_lib.lib().mft_dist_head_sgd_run(_p(z_support), _p(y_support), _p(table), G, S, D, n_way, table.shape[1],
+                                                table.shape[2], _p(v), _p(g), float(scale), lr, momentum, dampening, weight_decay,
+                                                _stream()), "mft_dist_head_sgd_run")
+
+
 def adam_hyper_advance(step_i32, hyper, lr=0.01, beta1=0.9, beta2=0.999):
     """Device-side t = ++step; hyper = {lr/(1-beta1^t), 1/sqrt(1-beta2^t)} (one tiny launch; graph-capturable)."""
     _lib.check(_lib.lib().mft_adam_hyper_advance(_p(step_i32), _p(hyper), lr, beta1, beta2, _stream()), "mft_adam_hyper_advance")

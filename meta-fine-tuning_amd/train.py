@@ -1,4 +1,4 @@
-"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / baseline): Adam over all parameters, 100
+"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / baseline / baseline++): Adam over all parameters, 100
 episodes per epoch, checkpoints ``{'epoch','state'}`` under <save_dir>/checkpoints/<dataset>/<model>_<method>
 [_aug]_<n>way_<k>shot/<epoch>.tar, optional first-order-MAML meta-fine-tuning (--fine_tune).
 The episode source is the in-repo synthetic miniImageNet-shaped sampler (real data is out of scope)."""
@@ -183,7 +183,7 @@ def train(base_loader, model, optimization, start_epoch, stop_epoch, params, var
     fifty = variant50 and params.n_shot == 50
     for epoch in range(start_epoch, stop_epoch):
         model.train()
-        if params.method == 'baseline':
+        if params.method in ('baseline', 'baseline++'):
             model.train_loop(epoch, base_loader, optimizer)              # train.py:41-42: every other method -> train_loop
         elif not params.fine_tune and getattr(params, "episodes_per_rank", 1) > 1:
             if fifty and params.method != 'protonet':
@@ -222,17 +222,18 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     rank, W = parallel.world()
     if not params.start_epoch > 0:
         np.random.seed(10)
-    if params.method not in ('gnnnet', 'baseline', 'protonet'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'protonet' and 'baseline' are on the HIP path" % params.method)
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'baseline' and 'baseline++' are on the HIP path" % params.method)
     if params.method == 'protonet' and params.fine_tune:
         raise NotImplementedError("--method protonet --fine_tune: ProtoNet's first-order-MAML meta-training is not on the HIP path")
     params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model, params.method)
     if params.train_aug:
         params.checkpoint_dir += '_aug'
-    if params.method == 'baseline':                                      # train.py:101-108,176-180
+    if params.method in ('baseline', 'baseline++'):                      # train.py:101-108,176-180
         from .methods.baselinetrain import BaselineTrain
         base_loader = SyntheticBatchLoader(params.num_classes, size, 16, n_episode)
-        model = BaselineTrain(model_dict[params.model], params.num_classes).cuda()
+        loss_type = 'dist' if params.method == 'baseline++' else 'softmax'
+        model = BaselineTrain(model_dict[params.model], params.num_classes, loss_type=loss_type).cuda()
     else:
         n_query = max(1, int(16 * params.test_n_way / params.train_n_way))
         # every rank draws its own episodes (rank r takes episode r, r+W, ... of the epoch's stream); same model init on all
