@@ -493,6 +493,20 @@ int mft_dist_head_sgd_run(const float* z_support, const int* y_support, const in
                           int D, int n_way, int n_steps, int batch_size, float* V, float* g, float s, float lr, float momentum,
                           float dampening, float weight_decay, void* stream);
 
+/* finetune_linear (finetune.py:45-174) with a distLinear(D, n_way) head per episode (group): the cosine counterpart of
+ * mft_linear_head_step, ONE launch for one inner step of all groups.  With the symbols above (eps_n = 1e-5) on the group's
+ * rows_per_group rows of feat (row stride ldf): scores s g_c u[r,c]; loss[grp] (nullable) = their mean cross entropy against
+ * labels [n_groups * rows_per_group], G = (softmax - onehot) / rows_per_group; dfeat (row stride lddf; every element written
+ * once) = the dx formula of mft_dist_linear_backward with the PRE-update V and g (zero row: dxh / eps_n, no NaN); then
+ * torch.optim.Adam(lr, betas, eps, L2 weight_decay) on V [n_groups, n_way, D] and g [n_groups, n_way] with the dV / dg formulas
+ * above and the moments mV, vV, mg, vg (weight decay joins both gradients; bias corrections on the host in double precision, as
+ * mft_linear_head_step).  One 256-thread workgroup per group, static LDS, no atomics: two launches are bit-identical.
+ * MFT_EINVAL outside rows_per_group 1..16, n_way 1..16, D <= 512 a multiple of 4, ldf / lddf >= D and multiples of 4,
+ * n_groups >= 1, step >= 1, 16-byte aligned feat / V / dfeat / mV / vV. */
+int mft_dist_head_step(const float* feat, int ldf, const int* labels, int rows_per_group, int n_groups, int n_way, int D, float s,
+                       float* V, float* g, float* mV, float* vV, float* mg, float* vg, float* dfeat, int lddf, float* loss,
+                       int step, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
 /* optimisers --------------------------------------------------------------------------- */
 /* torch.optim.Adam.step (finetune.py:255,299; gnnnet.py:128,177; train.py:28), one flat slab of n floats:
  * g += wd*p; m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g*g; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps) */

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mft_dist_linear_forward": [_P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P],
     "mft_dist_linear_backward": [_P, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _P],
     "mft_dist_head_sgd_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P],
+    "mft_dist_head_step": [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _F, _P],
     "mft_cross_entropy_mean": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
     "mft_cross_entropy_mean_backward": [_P, _I, _P, _I, _I, _I, _P, _P, _I, _P],
     "mft_adam_step": [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P],

@@ -343,6 +343,160 @@ __global__ __launch_bounds__(DL_THREADS) void dist_head_sgd_kernel(const float* 
     if (tid < n_way) g[(long long)grp * n_way + tid] = gs[tid];
 }
 
+// ------------------------------------------------------------------------------- test-time head step (FinetuneEngine "dist")
+// The cosine counterpart of linear_head_step_kernel (csrc/loss_optim.hip): one inner step of finetune_linear with a
+// distLinear(D, n_way) head for all episodes of the batch, one workgroup per episode (group).  feat -> scores -> mean cross
+// entropy -> dfeat (pre-update V, g) -> Adam with L2 weight decay on V and g.  k <= 16 rows, n_way <= 16.
+//   (A) wave tasks: ||v_c|| for class wave, wave + 4, ...; for row wave, wave + 4, ...: n_r and x_r . v_c for every class;
+//   (B) one thread per row: u, logits s g_c u, softmax, G = (p - onehot) / k, the row's loss; one thread per class: s g_c / ||v_c||;
+//   (C) one wave per row: dxh_r = sum_c G[r,c] (s g_c / ||v_c||) v_c in class order, dx_r as in the backward kernel; thread 0: loss;
+//   (D) behind a barrier (every read of V and g for dfeat is done): one thread per float4 of V: dv as in the run kernel with
+//       P_c = sum_r G[r,c] u[r,c], weight decay, Adam; n_way threads do the same for g (they read g only through phase B's LDS copy).
+constexpr int DH_MAX = 16;
+
+__global__ __launch_bounds__(DL_THREADS) void dist_head_step_kernel(
+    const float* __restrict__ feat, int ldf, const int* __restrict__ labels, int k, int n_way, int D, float s,
+    float* __restrict__ V, float* __restrict__ g, float* __restrict__ mV, float* __restrict__ vV, float* __restrict__ mg,
+    float* __restrict__ vg, float* __restrict__ dfeat, int lddf, float* __restrict__ loss, float step_size, float inv_sqrt_bc2,
+    float b1, float b2, float c1, float c2, float eps, float wd) {
+    __shared__ float sU[DH_MAX][DH_MAX];       // x_r . v_c, then u[r,c]
+    __shared__ float sG[DH_MAX][DH_MAX];       // G[r,c]
+    __shared__ float s_n[DH_MAX];              // n_r
+    __shared__ float s_inv[DH_MAX];            // 1 / (n_r + eps_n)
+    __shared__ float s_inv_nv[DH_MAX];         // 1 / ||v_c||
+    __shared__ float s_cf[DH_MAX];             // s g_c / ||v_c||
+    __shared__ float s_g[DH_MAX];              // g_c before the update
+    __shared__ float s_loss[DH_MAX];
+    const int grp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, d4 = D >> 2;
+    const float* F = feat + (long long)grp * k * ldf;
+    float* Vg = V + (long long)grp * n_way * D;
+    float* gg = g + (long long)grp * n_way;
+    // (A)
+    for (int c = wave; c < n_way; c += DL_WAVES) {
+        DlRow vc;
+        dl_load(vc, Vg + (long long)c * D, d4, lane);
+        const float nv = sqrtf(wave_sum(dl_dot(vc, vc)));
+        if (lane == 0) s_inv_nv[c] = 1.f / nv;
+    }
+    for (int r = wave; r < k; r += DL_WAVES) {
+        DlRow xr, vc, vn;
+        dl_load(xr, F + (long long)r * ldf, d4, lane);
+        dl_load(vc, Vg, d4, lane);
+        const float n = sqrtf(wave_sum(dl_dot(xr, xr)));
+        if (lane == 0) { s_n[r] = n; s_inv[r] = 1.f / (n + DL_EPS); }
+        for (int c = 0; c < n_way; ++c) {
+            if (c + 1 < n_way) dl_load(vn, Vg + (long long)(c + 1) * D, d4, lane);
+            const float d = wave_sum(dl_dot(xr, vc));
+            if (lane == 0) sU[r][c] = d;
+#pragma unroll
+            for (int i = 0; i < DL_MAX_V4; ++i) vc[i] = vn[i];
+        }
+    }
+    __syncthreads();
+    // (B)
+    if (tid < k) {
+        const int r = tid;
+        const int y = labels[(long long)grp * k + r];
+        const float ir = s_inv[r];
+        float mx = -3.4e38f;
+        for (int c = 0; c < n_way; ++c) {
+            const float u = sU[r][c] * ir * s_inv_nv[c];
+            const float lg = s * gg[c] * u;
+            sU[r][c] = u;
+            sG[r][c] = lg;
+            mx = fmaxf(mx, lg);
+        }
+        float se = 0.f;
+        for (int c = 0; c < n_way; ++c) se += expf(sG[r][c] - mx);
+        const float lse = mx + logf(se);
+        const float ik = 1.f / (float)k;
+        float ly = 0.f;
+        for (int c = 0; c < n_way; ++c) {
+            const float lg = sG[r][c];
+            if (c == y) ly = lg;
+            sG[r][c] = (expf(lg - lse) - (c == y ? 1.f : 0.f)) * ik;
+        }
+        s_loss[r] = lse - ly;
+    } else if (tid >= 64 && tid < 64 + n_way) {
+        const int c = tid - 64;
+        const float gc = gg[c];
+        s_g[c] = gc;
+        s_cf[c] = s * gc * s_inv_nv[c];
+    }
+    __syncthreads();
+    // (C)
+    if (tid == 0 && loss != nullptr) {
+        float t = 0.f;
+        for (int r = 0; r < k; ++r) t += s_loss[r];
+        loss[grp] = t / (float)k;
+    }
+    for (int r = wave; r < k; r += DL_WAVES) {
+        DlRow xr, vc, vn, dxh;
+        dl_load(xr, F + (long long)r * ldf, d4, lane);
+        dl_load(vc, Vg, d4, lane);
+#pragma unroll
+        for (int i = 0; i < DL_MAX_V4; ++i) dxh[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < n_way; ++c) {
+            if (c + 1 < n_way) dl_load(vn, Vg + (long long)(c + 1) * D, d4, lane);
+            const float coef = sG[r][c] * s_cf[c];
+#pragma unroll
+            for (int i = 0; i < DL_MAX_V4; ++i) {
+                dxh[i] += coef * vc[i];
+                vc[i] = vn[i];
+            }
+        }
+        const float n = s_n[r], ie = s_inv[r];
+        const float p = wave_sum(dl_dot(dxh, xr));
+        const float k2 = n > 0.f ? p * ie * ie / n : 0.f;
+#pragma unroll
+        for (int i = 0; i < DL_MAX_V4; ++i) dxh[i] = dxh[i] * ie - xr[i] * k2;
+        dl_store(dfeat + ((long long)grp * k + r) * lddf, dxh, d4, lane);
+    }
+    __syncthreads();
+    // (D)
+    f32x4* mVg = (f32x4*)(mV + (long long)grp * n_way * D);
+    f32x4* vVg = (f32x4*)(vV + (long long)grp * n_way * D);
+    for (int i = tid; i < n_way * d4; i += DL_THREADS) {
+        const int c = i / d4, j = i - c * d4;
+        f32x4 A = {0.f, 0.f, 0.f, 0.f};
+        float P = 0.f;
+        for (int r = 0; r < k; ++r) {
+            const float grc = sG[r][c];
+            P += grc * sU[r][c];
+            A += (grc * s_inv[r]) * *(const f32x4*)(F + (long long)r * ldf + 4 * j);
+        }
+        f32x4 w = ((f32x4*)Vg)[i], m = mVg[i], v = vVg[i];
+        const f32x4 gr = s_cf[c] * (A - (P * s_inv_nv[c]) * w) + wd * w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            m[e] = b1 * m[e] + c1 * gr[e];
+            v[e] = b2 * v[e] + c2 * gr[e] * gr[e];
+            w[e] = w[e] - step_size * (m[e] / (sqrtf(v[e]) * inv_sqrt_bc2 + eps));
+        }
+        mVg[i] = m;
+        vVg[i] = v;
+        ((f32x4*)Vg)[i] = w;
+    }
+    if (tid < n_way) {
+        const int c = tid;
+        float P = 0.f;
+        for (int r = 0; r < k; ++r) P += sG[r][c] * sU[r][c];
+        const float w = s_g[c];
+        const float gr = s * P + wd * w;
+        const long long i = (long long)grp * n_way + c;
+        const float m = b1 * mg[i] + c1 * gr;
+        const float v = b2 * vg[i] + c2 * gr * gr;
+        mg[i] = m;
+        vg[i] = v;
+        gg[c] = w - step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
+    }
+}
+
+// torch.optim.Adam forms 1 - beta and the bias corrections in double from the decimal beta it was given (0.999 -> 0.001); a beta
+// that arrives here as a float is 1.3e-5 of 1 - beta away from that (1.f - 0.999f = 0.00099998713), which is the whole error of v
+// after a first step from zero moments.  -> the beta rounded to 7 decimals: the decimal itself, or within a float ulp of any other.
+double dl_beta_decimal(float beta) { return nearbyint((double)beta * 1e7) / 1e7; }
+
 bool dl_dims_ok(int C, int D) { return C >= 1 && C <= DL_MAX_C && D >= 4 && D <= 512 && (D & 3) == 0; }
 bool dl_rows_ok(const void* p, int ld, int D) { return p != nullptr && ld >= D && (ld & 3) == 0 && ((uintptr_t)p & 15) == 0; }
 
@@ -397,5 +551,22 @@ extern "C" int mft_dist_head_sgd_run(const float* z_support, const int* y_suppor
         hipLaunchKernelGGL((dist_head_sgd_kernel<false>), dim3(n_groups), dim3(DL_THREADS), head, (hipStream_t)stream, z_support,
                            y_support, idx_table, n_support_rows, D, n_way, n_steps, batch_size, V, g, s, lr, momentum, dampening,
                            weight_decay);
+    return mft_launch_status();
+}
+
+extern "C" int mft_dist_head_step(const float* feat, int ldf, const int* labels, int rows_per_group, int n_groups, int n_way, int D,
+                                  float s, float* V, float* g, float* mV, float* vV, float* mg, float* vg, float* dfeat, int lddf,
+                                  float* loss, int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  void* stream) {
+    if (step < 1 || n_groups < 1 || rows_per_group < 1 || rows_per_group > DH_MAX || n_way < 1 || n_way > DH_MAX) return MFT_EINVAL;
+    if (!dl_dims_ok(n_way, D) || !dl_rows_ok(feat, ldf, D) || !dl_rows_ok(dfeat, lddf, D)) return MFT_EINVAL;
+    if (!dl_rows_ok(V, D, D) || !dl_rows_ok(mV, D, D) || !dl_rows_ok(vV, D, D)) return MFT_EINVAL;
+    if (labels == nullptr || g == nullptr || mg == nullptr || vg == nullptr) return MFT_EINVAL;
+    const double b1d = dl_beta_decimal(beta1), b2d = dl_beta_decimal(beta2);
+    const double bc1 = 1.0 - pow(b1d, (double)step);
+    const double bc2 = 1.0 - pow(b2d, (double)step);
+    hipLaunchKernelGGL(dist_head_step_kernel, dim3(n_groups), dim3(DL_THREADS), 0, (hipStream_t)stream, feat, ldf, labels,
+                       rows_per_group, n_way, D, s, V, g, mV, vV, mg, vg, dfeat, lddf, loss, (float)((double)lr / bc1),
+                       (float)(1.0 / sqrt(bc2)), beta1, beta2, (float)(1.0 - b1d), (float)(1.0 - b2d), eps, weight_decay);
     return mft_launch_status();
 }

@@ -288,10 +288,12 @@ class FinetuneEngine:
         "linear": finetune.finetune_linear (finetune.py:45-174: per-episode Linear(512, n_way) classifier trained together
         with the last block over the ORIGINAL support images only; scores = softmax(classifier(features)));
         "proto": finetune.finetune with a ProtoNet model -- the inner loop of "gnn" unchanged, scores = softmax of the ProtoNet
-        head on the final-pass features (mft_proto_scores with its softmax epilogue; ``state`` needs only 'feature.*')."""
-        assert mode in ("gnn", "linear", "proto")
+        head on the final-pass features (mft_proto_scores with its softmax epilogue; ``state`` needs only 'feature.*');
+        "dist": "linear" with a per-episode Baseline++ head distLinear(512, n_way) in place of the Linear one (one
+        mft_dist_head_step launch per step; scores = one grouped mft_dist_linear_forward launch with its softmax epilogue)."""
+        assert mode in ("gnn", "linear", "proto", "dist")
         self.mode = mode
-        self.views = mode != "linear"      # the inner loop trains on every view (finetune()); "linear" on view 0 only
+        self.views = mode not in ("linear", "dist")      # the inner loop trains on every view (finetune()); "linear" / "dist" on view 0 only
         # ``graph``: capture one inner step (single stream) as a hipGraph and replay it for every step -- ~40 launches
         # become 3 (index copy, label copy, replay).  Measured: no gain (a step is a chain of dependent kernels bound by
         # per-kernel latency on the GPU, not by the host launch rate; DESIGN.md section 2); off by default.
@@ -354,6 +356,10 @@ class FinetuneEngine:
         if mode == "linear":
             self.cls = {k: torch.zeros((self.E, n_way, 512) if k.endswith("W") else (self.E, n_way), device=self.dev)
                         for k in ("W", "b", "mW", "vW", "mb", "vb")}
+        if mode == "dist":
+            self.cls = {k: torch.zeros((self.E, n_way, 512) if k.endswith("V") else (self.E, n_way), device=self.dev)
+                        for k in ("V", "g", "mV", "vV", "mg", "vg")}
+            self.dist_scale = 2.0 if n_way <= 200 else 10.0          # backbone.distLinear.scale_factor
         self.arena = Fn.Arena(self.dev)
         self.arena_trunk = Fn.Arena(self.dev)      # the frozen-trunk stream owns its own buffers / BN workspace
         self.adapt = AdaptState(self.E, self.dev)
@@ -552,6 +558,14 @@ class FinetuneEngine:
                                                      self.lr, 0.9, 0.999, 1e-8, 0.001, ops._stream())
             ops._lib.check(rc, "mft_linear_head_step")
             ce = None
+        elif self.mode == "dist":
+            # the same step with the cosine head: scores, CE, d feature (pre-update V, g), Adam(lr .01, wd .001) on V, g in one launch
+            c = self.cls
+            dlogits = self.arena.get("dist.dfeat%d" % k, (E * k, 512))
+            loss = self.arena.get("dist.loss", (E,))
+            ops.dist_head_step(feat, lab_dev, c["V"], c["g"], c["mV"], c["vV"], c["mg"], c["vg"], self.dist_scale, self.adapt.step,
+                               dfeat=dlogits, loss=loss, lr=self.lr, weight_decay=0.001)
+            ce = None
         else:
             # inner loss = CE on the pooled 512-d feature (finetune.py:286-291); fused with the pool/ReLU backward
             loss = self.arena.get("ce.loss", (E,))
@@ -733,6 +747,12 @@ class FinetuneEngine:
             ops._lib.check(rc, "mft_linear_head_scores")
             sc = sc.view(self.E, self.n_way, self.n_support + self.n_query, self.n_way)[:, :, self.n_support:]
             return sc.reshape(self.E, self.n_way * self.n_query, self.n_way), feats
+        if self.mode == "dist":
+            # as "linear": one train-mode pass over cat(support, query), then every episode's rows against its own head in ONE
+            # grouped launch (softmax epilogue); the query rows are sliced out class-major
+            sc = ops.dist_linear_forward(feats, self.cls["g"], self.cls["V"], self.dist_scale, softmax=True)
+            sc = sc.view(self.E, self.n_way, self.n_support + self.n_query, self.n_way)[:, :, self.n_support:]
+            return sc.reshape(self.E, self.n_way * self.n_query, self.n_way), feats
         if self.mode == "proto":
             # (a fresh tensor, as softmax_rows gives the gnn path: a deferred final pass must not overwrite the previous batch's)
             sc = ops.proto_scores(feats, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
@@ -751,6 +771,17 @@ class FinetuneEngine:
         idx = torch.clamp(torch.arange(self.E, device=self.dev), max=n_active - 1)
         c["W"].copy_(w0[idx])
         c["b"].copy_(b0[idx])
+
+    def set_dist_head(self, v0, g0, n_active):
+        """Initial distLinear(512, n_way) heads per episode: v0 [n, n_way, 512], g0 [n, n_way(, 1)] (finetune.dist_head_init)."""
+        c = self.cls
+        for k in ("mV", "vV", "mg", "vg"):
+            c[k].zero_()
+        v0 = torch.as_tensor(v0, dtype=torch.float32).to(self.dev).view(-1, self.n_way, 512)
+        g0 = torch.as_tensor(g0, dtype=torch.float32).to(self.dev).view(-1, self.n_way)
+        idx = torch.clamp(torch.arange(self.E, device=self.dev), max=n_active - 1)
+        c["V"].copy_(v0[idx])
+        c["g"].copy_(g0[idx])
 
     def _flip_buffers(self):
         """Deferred final pass: the adapted weights and final-pass images of batch i must survive while batch i+1 is ingested
@@ -837,6 +868,10 @@ class FinetuneEngine:
             if classifier_init is None:
                 raise RuntimeError("mode='linear' needs classifier_init=(w0 [n,n_way,512], b0 [n,n_way])")
             self.set_classifier(classifier_init[0], classifier_init[1], n)
+        if self.mode == "dist":
+            if classifier_init is None:
+                raise RuntimeError("mode='dist' needs classifier_init=(v0 [n,n_way,512], g0 [n,n_way])")
+            self.set_dist_head(classifier_init[0], classifier_init[1], n)
         if not prepared:
             self.prepare_batch()
         if prefetch is not None and defer_final and self.stem is not None and self.pipeline:

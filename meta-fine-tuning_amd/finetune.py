@@ -10,7 +10,7 @@ RNG).  Three ways in, same arithmetic and same permutation stream:
   episodes ahead, runs them as one lockstep batch (drawing their permutations in the order the sequential calls would) and
   the per-episode ``finetune()`` / ``finetune_linear()`` calls of the loop body return the finished scores.
 
-``main`` mirrors the reference's ``__main__``: ``--method gnnnet | baseline | all``, ``--freeze_backbone``,
+``main`` mirrors the reference's ``__main__``: ``--method gnnnet | baseline | baseline++ | all``, ``--freeze_backbone``,
 ``--n_shot 50`` (gnnnet_copy, as finetune_50.py:20).  Launched under ``torchrun`` it shards the 600 episodes over the ranks
 (parallel.shard_indices, one all-gather of accuracies at the end -- SURVEY.md §8(e)).  Checkpoints are looked up where the reference looks
 (``checkpoint_files``, finetune.py:448-527); real datasets are out of scope: episodes are the in-repo
@@ -91,6 +91,7 @@ class _EngineCache:
 
 _ENGINES = _EngineCache(3)
 _LIN_ENGINES = _EngineCache(2)
+_DIST_ENGINES = _EngineCache(2)
 
 
 def _head_key(model):
@@ -127,9 +128,18 @@ def _linear_engine(state_in, n_way, n_support, n_query, size, n_views, E):
     return _LIN_ENGINES.get(state_in, cfg, build)
 
 
+def _dist_engine(state_in, n_way, n_support, n_query, size, n_views, E):
+    cfg = ("dist", n_way, n_support, n_query, size, n_views, E)
+
+    def build():
+        return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=LINEAR_EPOCHS,
+                                  episodes_per_batch=E, mode="dist")
+    return _DIST_ENGINES.get(state_in, cfg, build)
+
+
 # ------------------------------------------------------------------------------------------------ lookahead registry
 
-_READY = {}            # id(first view tensor) -> {"pin": tensor, "gnn": scores | None, "linear": scores | None, "ctx": {...}}
+_READY = {}            # id(first view tensor) -> {"pin": tensor, "gnn" / "linear" / "dist": scores | None, "ctx": {...}}
 
 
 def _take_ready(liz_x, kind, freeze_backbone=False, state_in=None, model=None):
@@ -149,7 +159,7 @@ def _take_ready(liz_x, kind, freeze_backbone=False, state_in=None, model=None):
                            "with the arguments the loop body passes" % (kind, ctx["freeze_backbone"], bool(freeze_backbone)))
     sc = ent[kind]
     ent[kind] = None
-    if ent.get("gnn") is None and ent.get("linear") is None:
+    if ent.get("gnn") is None and ent.get("linear") is None and ent.get("dist") is None:
         del _READY[id(liz_x[0])]
     return sc
 
@@ -290,7 +300,7 @@ def draw_episode_perms(method, n_way, n_support, n_views, fine_tune_epoch, rng=n
     finetune_linear's 20 permutations of the support set (finetune.py:139-141), then ``all`` / ``gnnnet`` draw finetune's
     ``fine_tune_epoch`` permutations of n_way*n_support*(n_views+1) (finetune.py:269-272).  -> (linear perms | None, gnn perms | None)"""
     lin = gnn = None
-    if method in ("all", "baseline"):
+    if method in ("all", "baseline", "baseline++"):          # (finetune_dist is finetune_linear's loop: the same 20 draws)
         lin = [rng.permutation(n_way * n_support) for _ in range(LINEAR_EPOCHS)]
     if method in ("all", "gnnnet", "protonet"):
         gnn = [rng.permutation(n_way * n_support * (n_views + 1)) for _ in range(fine_tune_epoch)]
@@ -374,10 +384,58 @@ def baselinepp_batched(episodes, state_in, n_way=5, n_support=5, episodes_per_ba
     return torch.cat(out)
 
 
+def _finetune_dist(P, liz_x, y, state_in, save_it, linear=False, flatten=True, n_query=15, ds=False,
+                   pretrained_dataset='miniImageNet', freeze_backbone=False, n_way=5, n_support=5, head=None):
+    if not flatten:
+        raise NotImplementedError("finetune_dist(): flatten=False is outside the HIP hot path")
+    ready = _take_ready(liz_x, "dist", freeze_backbone, state_in)
+    if ready is not None:
+        return ready
+    x0 = liz_x[0]
+    n_query = x0.size(1) - n_support
+    heads = None if head is None else (torch.as_tensor(head[0]).view(1, n_way, -1), torch.as_tensor(head[1]).view(1, n_way, 1))
+    if freeze_backbone:
+        return baselinepp_batched([liz_x], state_in, n_way, n_support, 1, heads=heads)
+    e = _dist_engine(state_in, n_way, n_support, n_query, x0.size(-1), len(liz_x), 1)
+    v0, g0 = dist_head_init(n_way) if heads is None else heads
+    return e.run_batch([liz_x], classifier_init=(v0, g0))[0].clone()
+
+
+def finetune_dist(liz_x, y, state_in, save_it, linear=False, flatten=True, n_query=15, ds=False,
+                  pretrained_dataset='miniImageNet', freeze_backbone=False, n_way=5, n_support=5, head=None):
+    """Baseline++ at test time: the reference's finetune_linear (finetune.py:45-174) with ``Classifier`` replaced by
+    ``distLinear(512, n_way)`` -- 20 epochs over the ORIGINAL support images in mini-batches of 5, Adam(0.01,
+    weight_decay=0.001) on the head and Adam(0.01) on trunk.7, scores = softmax(head(features of the queries)).  ``head`` =
+    (v0 [n_way, 512], g0 [n_way, 1]) pins the initial head (default: one ``dist_head_init`` draw from torch's global RNG).
+    ``freeze_backbone=True`` is Baseline++'s OWN protocol instead (``baselinepp_batched``: eval-mode features, 100 epochs of
+    SGD on the head alone), not a frozen variant of the loop above."""
+    return _finetune_dist(params, liz_x, y, state_in, save_it, linear, flatten, n_query, ds, pretrained_dataset,
+                          freeze_backbone, n_way, n_support, head)
+
+
+def finetune_dist_batched(episodes, state_in, n_way=5, n_support=5, episodes_per_batch=32, perms=None, heads=None):
+    """finetune_dist over a list of episodes in lockstep (FinetuneEngine(mode="dist")).  ``perms[i]``: the 20 permutations of the
+    support set of episode i (default: drawn episode by episode from the global numpy RNG); ``heads`` = (v0 [n, n_way, 512],
+    g0 [n, n_way, 1]); default: one ``dist_head_init`` draw per episode from torch's global RNG, in episode order."""
+    x0 = episodes[0][0]
+    n_query = x0.size(1) - n_support
+    e = _dist_engine(state_in, n_way, n_support, n_query, x0.size(-1), len(episodes[0]), episodes_per_batch)
+    if heads is None:
+        heads = dist_head_init(n_way, n=len(episodes))
+    out = []
+    for i in range(0, len(episodes), episodes_per_batch):
+        chunk = episodes[i:i + episodes_per_batch]
+        p = None if perms is None else perms[i:i + episodes_per_batch]
+        hi = (heads[0][i:i + len(chunk)], heads[1][i:i + len(chunk)])
+        out.append(e.run_batch(chunk, perms=p, classifier_init=hi).clone())
+    return torch.cat(out)
+
+
 def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch, n_way=5, n_support=5, episodes_per_batch=32,
                    rngs=None, classifiers=None, parts=False):
     """What the reference's loop body computes for each episode of ``episodes`` (finetune.py:615-619,647-649), in lockstep:
-    ``gnnnet`` / ``protonet`` -> finetune(); ``baseline`` -> finetune_linear(); ``all`` -> their sum.  The permutations of all episodes are
+    ``gnnnet`` / ``protonet`` -> finetune(); ``baseline`` -> finetune_linear(); ``baseline++`` -> finetune_dist() (its scores take the
+    linear slot, ``classifiers`` = its heads (v0, g0)); ``all`` -> finetune_linear() + finetune().  The permutations of all episodes are
     drawn FIRST, episode by episode in the order the sequential calls would draw them (from the global numpy RNG, or from
     ``rngs[i]`` -- one generator per episode, the rank-count-invariant stream of parallel.episode_rng).
     ``parts``: return (linear scores | None, gnn scores | None) instead of the sum."""
@@ -391,6 +449,8 @@ def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch,
     s_lin = s_gnn = None
     if method in ("all", "baseline"):
         s_lin = finetune_linear_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, classifiers=classifiers)
+    if method == "baseline++":
+        s_lin = finetune_dist_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, heads=classifiers)
     if method in ("all", "gnnnet", "protonet"):
         s_gnn = finetune_batched(episodes, model, state_gnn, fine_tune_epoch, n_way, n_support, episodes_per_batch, perms=gnn_p)
     if parts:
@@ -456,7 +516,7 @@ class LookaheadLoader:
             for j, elem in enumerate(batch):
                 pin = elem[0][0]
                 _READY[id(pin)] = {"pin": pin, "gnn": None if s_gnn is None else s_gnn[j],
-                                   "linear": None if s_lin is None else s_lin[j], "ctx": ctx}
+                                   "dist" if self.method == "baseline++" else "linear": None if s_lin is None else s_lin[j], "ctx": ctx}
                 issued.append(id(pin))
             for elem in batch:
                 yield elem
@@ -531,6 +591,9 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
     while batch b adapts; for ``--method gnnnet`` batch b+1's ingest + stem cache run beside batch b's inner loop and batch b's
     final pass + GNN head beside batch b+1's first steps (FinetuneEngine.run_batch(defer_final=, prefetch=)); accuracies are
     read from the device once, at the end.  ``balance``: equalise the batch sizes (``balanced_batch``).
+    ``method="baseline++"`` (``state_b`` = the Baseline++ checkpoint, ``model`` unused): ``finetune_dist`` in lockstep, the heads
+    drawn like ``classifier_init``'s; with ``freeze_backbone=True`` it is Baseline++'s own protocol -- eval-mode features and 100
+    epochs of SGD on the head alone -- through ONE ``baselinepp_batched`` call per batch.
     ``sampler``: an augment.EpisodeSampler over a uint8 dataset resident in HBM -- episode i is then ``sampler.episode(seed0 + i)``
     (classes = randperm(n_classes)[:n_way], per class n_shot + n_query distinct random images, datasets/EuroSAT_few_shot.py:
     75-124,329-351) and its 2 + gen_examples views are generated on the device (mft_augment_views) straight into the engine's
@@ -625,15 +688,20 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
         rngs = cls = None
         if rng_seed is not None:
             rngs = [parallel.episode_rng(rng_seed, i) for i in ids]
-            if method in ("all", "baseline"):
+            if method in ("all", "baseline", "baseline++"):
                 ws, bs = [], []
                 for i in ids:
                     with torch.random.fork_rng(devices=[]):
                         torch.manual_seed(parallel.episode_torch_seed(rng_seed, i))
-                        w, b = classifier_init(n_way)
+                        w, b = dist_head_init(n_way) if method == "baseline++" else classifier_init(n_way)
                     ws.append(w[0]); bs.append(b[0])
                 cls = (torch.stack(ws), torch.stack(bs))
-        if freeze_backbone:
+        if freeze_backbone and method == "baseline++":
+            S = n_way * n_shot
+            perms = [[(np.random if rngs is None else rngs[k]).permutation(S) for _ in range(BASELINEPP_EPOCHS)] for k in range(len(eps))]
+            sc = baselinepp_batched(eps, state_b, n_way, n_shot, episodes_per_batch, perms=perms, heads=cls)
+            sc = sc.view(len(eps), n_way * n_query, n_way)
+        elif freeze_backbone:
             sc = []
             for k, ep in enumerate(eps):
                 st = np.random.get_state()
@@ -695,6 +763,9 @@ def _score_one(method, liz_x, model, state, state_b, n_way, n_shot, fine_tune_ep
     if method == "baseline":
         return finetune_linear(liz_x, None, state_b, None, linear=True, freeze_backbone=freeze_backbone, n_way=n_way,
                                n_support=n_shot, classifier=classifier)
+    if method == "baseline++":
+        return finetune_dist(liz_x, None, state_b, None, linear=True, freeze_backbone=freeze_backbone, n_way=n_way,
+                             n_support=n_shot, head=classifier)
     if method == "all":
         return finetune_all(liz_x, None, model, state_b, state, n_way, n_shot, classifier=classifier, freeze_backbone=freeze_backbone)
     return finetune(liz_x, None, model, state, None, freeze_backbone=freeze_backbone, n_way=n_way, n_support=n_shot)
@@ -753,6 +824,20 @@ def checkpoint_files(p):
     return f_gnn, f_b
 
 
+def baselinepp_checkpoint_file(p):
+    """The checkpoint ``--method baseline++`` evaluates: <save_dir>/checkpoints/miniImageNet/<model>_baseline++[_aug]/<save_iter>.tar,
+    or the newest epoch there (get_resume_file) with ``--save_iter -1`` -- the directory ``train.main --method baseline++``
+    writes.  The reference's own lookup for this method (finetune.py:519-527, the last case of ``checkpoint_files``) appends
+    ``_<n>way_<k>shot`` to the directory name, which its train.py never does for the two baselines (train.py:176-180): it can
+    never find the checkpoint, so this is a separate function and ``checkpoint_files`` stays the reference's."""
+    from . import configs
+    from .io_utils import get_assigned_file, get_resume_file
+    d = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, PRETRAINED_DATASET, p.model, "baseline++")
+    if p.train_aug:
+        d += '_aug'
+    return get_assigned_file(d, p.save_iter) if p.save_iter != -1 else get_resume_file(d)
+
+
 def load_checkpoint_state(modelfile):
     """``torch.load(modelfile)['state']`` minus the ``feature2.`` / ``feature3.`` entries a --fine_tune run leaves behind
     (finetune.py:498-512,531-540; train.py:197-202).  Tensors stay on the host: the engine packs its own device copies."""
@@ -769,8 +854,8 @@ def standin_state(kind, n_way):
     seeded backbone + the GNN head that was meta-trained with the REFERENCE's set_forward_loss for accuracy golden G9
     (tests/golden/g9_head.npz) -- the printed accuracy is then a real one (~90 % on the synthetic episodes at the README
     settings), not the below-chance score of a random head.  ``baseline``: a seeded backbone (finetune_linear trains its own
-    classifier)."""
-    if kind == "baseline":
+    classifier); ``baseline++``: the same seeded backbone (finetune_dist trains its own head)."""
+    if kind in ("baseline", "baseline++"):
         return synthetic.gnnnet_state_dict(seed=400, n_way=n_way)
     head = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g9_head.npz")
     if n_way == 5 and os.path.isfile(head):
@@ -810,9 +895,10 @@ def _resolve_state(kind, modelfile, n_way, explicit, verbose):
 
 def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
     """finetune.py:424-682.  ``--method gnnnet`` (and gnnnet at ``--n_shot 50`` through gnnnet_copy, finetune_50.py),
-    ``--method baseline`` (finetune_linear on the baseline checkpoint), ``--method all`` (their sum).  Checkpoints are looked
-    up exactly where the reference looks (``checkpoint_files``): what ``train.main --dataset miniImageNet`` wrote under
-    ``configs.save_dir`` is what this evaluates."""
+    ``--method baseline`` (finetune_linear on the baseline checkpoint), ``--method all`` (their sum), ``--method baseline++``
+    (finetune_dist on the Baseline++ checkpoint).  Checkpoints are looked up exactly where the reference looks
+    (``checkpoint_files``; ``baselinepp_checkpoint_file`` for baseline++, whose reference lookup cannot succeed): what
+    ``train.main --dataset miniImageNet`` wrote under ``configs.save_dir`` is what this evaluates."""
     global params
     np.random.seed(10)                                               # finetune.py:425
     params = parse_args('train', argv)
@@ -821,9 +907,9 @@ def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
     rank, _W = parallel.world()
     from .methods.gnnnet import GnnNet
     from .methods import gnnnet_copy
-    if params.method not in ('gnnnet', 'baseline', 'all'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'baseline' and 'all' are on the HIP hot path (protonet / relationnet / "
-                                  "dampnet are out of scope, SURVEY.md §2.1)" % params.method)
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'all'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'baseline', 'baseline++' and 'all' are on the HIP hot path (protonet / "
+                                  "relationnet / dampnet are out of scope, SURVEY.md §2.1)" % params.method)
     cfg = settings.current()
     size = cfg.image_size
     n_episodes = n_episodes if cfg.episodes is None else cfg.episodes
@@ -832,8 +918,8 @@ def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
     if episodes_per_batch is None:
         episodes_per_batch = cfg.episodes_per_batch if cfg.episodes_per_batch is not None else {5: 128, 20: 96, 50: 64}.get(params.n_shot, 32)
     model = state = state_b = None
-    f_gnn, f_b = checkpoint_files(params)
-    main.loaded = {"gnnnet": None, "baseline": None}                 # what was actually read (tests, logs)
+    f_gnn, f_b = (None, baselinepp_checkpoint_file(params)) if params.method == 'baseline++' else checkpoint_files(params)
+    main.loaded = {"gnnnet": None, "baseline": None, "baseline++": None}       # what was actually read (tests, logs)
     if params.method in ('gnnnet', 'all'):
         model = model_cls(model_dict[params.model], n_way=params.test_n_way, n_support=params.n_shot).cuda()
         # `all` names 600.tar by literal, gnnnet names <save_iter>.tar: both explicit unless --save_iter is -1 for gnnnet
@@ -842,7 +928,9 @@ def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
         model.load_state_dict(state)                                 # finetune.py:512,540
     if params.method in ('baseline', 'all'):
         state_b, main.loaded["baseline"] = _resolve_state("baseline", f_b, params.test_n_way, params.save_iter != -1, rank == 0)
-    used = [k for k in ("gnnnet", "baseline") if params.method in (k, "all")]
+    if params.method == 'baseline++':
+        state_b, main.loaded["baseline++"] = _resolve_state("baseline++", f_b, params.test_n_way, params.save_iter != -1, rank == 0)
+    used = ["baseline++"] if params.method == 'baseline++' else [k for k in ("gnnnet", "baseline") if params.method in (k, "all")]
     print(params.freeze_backbone)                                    # finetune.py:591
     tm = {} if cfg.timings else None
     if tm is not None:

@@ -951,6 +951,36 @@ def dist_head_sgd_run(z_support, y_support, table, v, g, scale, lr=0.01, momentu
                                                 _stream()), "mft_dist_head_sgd_run")
 
 
+def dist_head_step(feat, labels, v, g, mv, vv, mg, vg, scale, step, dfeat=None, loss=None, lr=0.01, beta1=0.9, beta2=0.999,
+                   eps=1e-8, weight_decay=0.001):
+    """One inner step of finetune_linear with a distLinear head for every group, one launch: feat [G * k, D] (row stride free),
+    labels [G * k] int32, v [G, n_way, D] and g [G, n_way] with their Adam moments (all six updated IN PLACE with
+    torch.optim.Adam semantics, L2 weight decay); ``step`` = the 1-based Adam step.  -> (dfeat [G * k, D] computed with the
+    pre-update head, loss [G]); both are written whole (``dfeat`` / ``loss``: caller's buffers)."""
+    _dist_rows(feat, "dist_head_step")
+    for t in (v, g, mv, vv, mg, vg):
+        _f32c(t)
+    if labels.dtype != torch.int32 or not labels.is_contiguous():
+        raise RuntimeError("dist_head_step: labels must be a contiguous int32 tensor")
+    if v.dim() != 3:
+        raise ValueError("dist_head_step: v must be [groups, n_way, D], got %s" % (tuple(v.shape),))
+    G, n_way, D = v.shape
+    k = feat.shape[0] // max(G, 1)
+    if G < 1 or feat.shape[0] != G * k or feat.shape[1] != D or labels.numel() != G * k or g.numel() != G * n_way \
+            or any(t.shape != v.shape for t in (mv, vv)) or any(t.numel() != G * n_way for t in (mg, vg)):
+        raise ValueError("dist_head_step: feat %s, labels %s, v %s, g %s and their moments do not fit"
+                         % (tuple(feat.shape), tuple(labels.shape), tuple(v.shape), tuple(g.shape)))
+    if dfeat is None:
+        dfeat = torch.empty((G * k, D), device=feat.device, dtype=torch.float32)
+    if loss is None:
+        loss = torch.empty((G,), device=feat.device, dtype=torch.float32)
+    _dist_rows(dfeat, "dist_head_step")
+    _lib.check(_lib.lib().mft_dist_head_step(_p(feat), feat.stride(0), _p(labels), k, G, n_way, D, float(scale), _p(v), _p(g),
+                                             _p(mv), _p(vv), _p(mg), _p(vg), _p(dfeat), dfeat.stride(0), _p(loss), int(step), lr,
+                                             beta1, beta2, eps, weight_decay, _stream()), "mft_dist_head_step")
+    return dfeat, loss
+
+
 def adam_hyper_advance(step_i32, hyper, lr=0.01, beta1=0.9, beta2=0.999):
     """Device-side t = ++step; hyper = {lr/(1-beta1^t), 1/sqrt(1-beta2^t)} (one tiny launch; graph-capturable)."""
     _lib.check(_lib.lib().mft_adam_hyper_advance(_p(step_i32), _p(hyper), lr, beta1, beta2, _stream()), "mft_adam_hyper_advance")
