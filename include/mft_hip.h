@@ -463,6 +463,67 @@ int mft_proto_scores(const float* feats, int ld, int episodes, int n_way, int n_
 int mft_proto_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
                        const float* dscores, int ldg, float* dfeats, int ldd, void* stream);
 
+/* MatchingNet head (csrc/matchingnet.hip): fp32 throughout, accurate expf / tanhf, fixed summation orders
+ * (bit-identical reruns), the recurrence cut at launch boundaries.  D must be 512; S = n_way * n_support <= 256, n_way 1..32,
+ * n_support >= 1, n_query >= 1, episodes >= 1; MFT_EINVAL outside (nothing is launched).
+ *
+ * mft_mn_gemm: c[z] = c_in[z] + bias1 + bias2 + op(a1[z]) op(b1[z]) + op(a2[z]) op(b2[z]) for z < batch; op(a) is [M, K] (transa:
+ * stored [K, M]), op(b) is [K, N] (transb: stored [N, K], the layout of an nn.Linear / LSTM weight); *_bs are (signed) element
+ * strides between batches; b1_alt (nullable, batch <= 2): batch 1 reads it instead of b1 + b1_bs (the two directions of
+ * G_encoder are separate tensors).  A pair with K = 0 is skipped; c_in, bias1, bias2 nullable; c_in may be c.  k runs in order.
+ * It carries the time-parallel input parts (z_S W_ih^T for all S steps), the per-step h W_hh^T (+ r W_ih[:, D:]^T) and every
+ * data / weight gradient of the head (weight gradients: ONE transposed GEMM over the rows of all time steps and episodes). */
+int mft_mn_gemm(int transa, int transb, int M, int N, int batch, const float* a1, int lda1, long long a1_bs, const float* b1,
+                const float* b1_alt, int ldb1, long long b1_bs, int K1, const float* a2, int lda2, long long a2_bs, const float* b2,
+                int ldb2, long long b2_bs, int K2, const float* c_in, int ldci, long long ci_bs, const float* bias1,
+                const float* bias2, float* c, int ldc, long long c_bs, void* stream);
+/* LSTM cell, torch gate order (i, f, g, o).  forward: gates [rows, 4D] (row stride ld_g) hold the pre-activations and leave with
+ * the activations; c' = f c_prev + i g (c_prev nullable = 0), h' = o tanh(c') + f_add (nullable: the FCE's "h += f").
+ * backward: gates hold the activations and leave with d(pre-activations); dh = dh1 + dh2 (dh2 nullable), dc_in nullable (= 0),
+ * dc_out = d(c_prev) (may be dc_in); dh_sum [rows, D] (+)= dh and dgate_sum [rows, 4D] (+)= d(pre-activations) (both nullable,
+ * batch 1 only; `accumulate` = 0 writes, 1 adds).  batch: independent cells (the two directions), *_bs their element strides. */
+int mft_lstm_step_forward(float* gates, int ld_g, long long bs_g, const float* c_prev, int ld_cp, long long bs_cp,
+                          const float* f_add, int ld_f, float* c_out, float* h_out, int ld_o, long long bs_o, int rows, int D,
+                          int batch, void* stream);
+int mft_lstm_step_backward(float* gates, int ld_g, long long bs_g, const float* c_prev, int ld_cp, long long bs_cp,
+                           const float* c_new, int ld_cn, long long bs_cn, const float* dh1, int ld_d1, long long bs_d1,
+                           const float* dh2, int ld_d2, long long bs_d2, const float* dc_in, float* dc_out, int ld_dc,
+                           long long bs_dc, float* dh_sum, float* dgate_sum, int accumulate, int rows, int D, int batch,
+                           void* stream);
+/* feats [episodes, n_way, n_support + n_query, D] (row stride ld) -> zS [episodes, S, D], zQ [episodes * Q, D] (query rows
+ * class-major) and h0 (nullable, a second copy of zQ: the FCE's first state); backward: dfeats support rows = dzS, query rows =
+ * dq1 + dq2 (dq2 nullable). */
+int mft_mn_gather(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, float* zS, float* zQ,
+                  float* h0, void* stream);
+int mft_mn_scatter_backward(const float* dzS, const float* dq1, const float* dq2, int episodes, int n_way, int n_support,
+                            int n_query, int D, float* dfeats, int ldd, void* stream);
+/* G = zS + h_forward + h_reverse [episodes, S, D], gnorm [episodes, S] = ||G_s||_2 */
+int mft_mn_encode_combine(const float* zS, const float* hf, const float* hr, int episodes, int S, int D, float* G, float* gnorm,
+                          void* stream);
+/* out[c] = sum_r x[r][c], rows in order (bias gradients) */
+int mft_mn_colsum(const float* x, int ldx, int C, long long rows, float* out, void* stream);
+/* Attention read of the FCE, one wave per query row (S > 64: several columns per lane): a [episodes * Q, S] = softmax(h G^T) with
+ * the episode's own G, r = a G.  backward: dlogit = a (da - sum a da) with da = dr G^T, dh_out = dh_in (nullable) + dlogit G; the
+ * gradient into G (a^T dr + dlogit^T h, a sum over query rows) is a batched mft_mn_gemm of the caller's. */
+int mft_mn_attention_forward(const float* h, const float* G, int episodes, int Q, int S, int D, float* a, float* r, void* stream);
+int mft_mn_attention_backward(const float* dr, const float* a, const float* G, const float* dh_in, int episodes, int Q, int S,
+                              int D, float* dlogit, float* dh_out, void* stream);
+/* Read-out: cos [episodes * Q, S] = F^ G^^T with F^ = h / (||h|| + 1e-5), G^ = G / (gnorm + 1e-5); p = softmax_S(100 relu(cos));
+ * pc [episodes * Q, n_way] = class sums of p; logp = log(pc + 1e-6); hnorm = ||h||.  backward (two kernels): dcos (scratch
+ * [episodes * Q, S]), dh and dG (every row written) through both normalisations; dlogp row stride ldg. */
+int mft_mn_readout_forward(const float* h, const float* G, const float* gnorm, int episodes, int n_way, int n_support, int n_query,
+                           int D, float* cosv, float* p, float* hnorm, float* pc, float* logp, void* stream);
+int mft_mn_readout_backward(const float* dlogp, int ldg, const float* h, const float* G, const float* gnorm, const float* cosv,
+                            const float* p, const float* hnorm, const float* pc, int episodes, int n_way, int n_support, int n_query,
+                            int D, float* dcos, float* dh, float* dG, void* stream);
+/* nn.NLLLoss(reduction='mean') on [rows, C] log-probabilities, labels int64 (labels_i64 = 1) or int32: loss[0] = -mean_r
+ * logp[r, y_r] summed in a fixed order; loss_sum (nullable, float64 device scalar) += loss, as mft_cross_entropy_mean keeps it.
+ * backward: dlogp[r, c] = -[c == y_r] grad_loss[0] / rows (grad_loss a DEVICE scalar, NULL = 1), every entry written. */
+int mft_nll_mean(const float* logp, int ld, const void* labels, int labels_i64, int C, int rows, float* loss, double* loss_sum,
+                 void* stream);
+int mft_nll_mean_backward(const void* labels, int labels_i64, int C, int rows, const float* grad_loss, float* dlogp, int ldd,
+                          void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

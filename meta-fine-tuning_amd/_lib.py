@@ -79,6 +79,19 @@ SIGNATURES = {
     "mft_softmax_rows": [_P, _I, _P, _I, _I, _I, _P],
     "mft_proto_scores": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     "mft_proto_backward": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
+    "mft_mn_gemm": [_I, _I, _I, _I, _I, _P, _I, _L, _P, _P, _I, _L, _I, _P, _I, _L, _P, _I, _L, _I, _P, _I, _L, _P, _P, _P, _I, _L, _P],
+    "mft_lstm_step_forward": [_P, _I, _L, _P, _I, _L, _P, _I, _P, _P, _I, _L, _I, _I, _I, _P],
+    "mft_lstm_step_backward": [_P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _P, _I, _L, _P, _P, _I, _I, _I, _I, _P],
+    "mft_mn_gather": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "mft_mn_scatter_backward": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
+    "mft_mn_encode_combine": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "mft_mn_colsum": [_P, _I, _I, _L, _P, _P],
+    "mft_mn_attention_forward": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "mft_mn_attention_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "mft_mn_readout_forward": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "mft_mn_readout_backward": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "mft_nll_mean": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "mft_nll_mean_backward": [_P, _I, _I, _I, _P, _P, _I, _P],
     "mft_dist_linear_forward": [_P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P],
     "mft_dist_linear_backward": [_P, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _P],
     "mft_dist_head_sgd_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P],

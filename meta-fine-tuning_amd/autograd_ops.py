@@ -388,3 +388,89 @@ def dist_linear(x, g, v, scale):
     if torch.is_grad_enabled() and (x.requires_grad or g.requires_grad or v.requires_grad):
         return _DistLinearFn.apply(x, g.contiguous(), v.contiguous(), float(scale))
     return ops.dist_linear_forward(x.detach(), g.detach().contiguous(), v.detach().contiguous(), float(scale))
+
+
+def matchingnet_params(model):
+    """The twelve head parameters of a MatchingNet in state-dict order (ops.MN_KEYS): FCE.lstmcell.*, G_encoder.*"""
+    named = dict(model.FCE.lstmcell.named_parameters(prefix="FCE.lstmcell"))
+    named.update(model.G_encoder.named_parameters(prefix="G_encoder"))
+    return [named[k] for k in ops.MN_KEYS]
+
+
+def _mn_weights(plist):
+    for k, p in zip(ops.MN_KEYS, plist):
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("MatchingNet head: parameter %s must be a contiguous float32 tensor on the GPU (no CPU fallback)" % k)
+    return {k: p.detach() for k, p in zip(ops.MN_KEYS, plist)}       # read in torch's own layout: no packed copies to refresh
+
+
+class _MatchingHeadFn(torch.autograd.Function):
+    """MatchingNet head (G_encoder, FCE, cosine read-out) with a hand-written backward: ops.matching_forward keeps the per-step
+    h, c, a, r and gates, ops.matching_backward walks the S FCE steps and the S encoder steps back and returns the gradients of the
+    features and of the twelve head parameters."""
+
+    @staticmethod
+    def forward(ctx, feats, n_way, n_support, n_query, episodes, *plist):
+        W = _mn_weights(plist)
+        logp, tape = ops.matching_forward(W, feats, episodes, n_way, n_support, n_query, save=True)
+        ctx.tape, ctx.W = tape, W
+        ctx.need = (feats.requires_grad,) + tuple(p.requires_grad for p in plist)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        if ctx.tape is None:
+            raise RuntimeError("MatchingNet head: backward called twice (the saved gates are consumed by the first pass)")
+        d = dlogp if (dlogp.dtype == torch.float32 and dlogp.stride(1) == 1) else dlogp.contiguous().float()
+        dfeats, g = ops.matching_backward(ctx.W, ctx.tape, d)
+        ctx.tape = None
+        out = [g[k] if need else None for k, need in zip(ops.MN_KEYS, ctx.need[1:])]
+        return (dfeats if ctx.need[0] else None, None, None, None, None) + tuple(out)
+
+
+def matchingnet_head(model, feats, n_support, n_query, episodes=1):
+    """MatchingNet.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one
+    episode after the other) -> log-probabilities [episodes*n_way*n_query, n_way].  Differentiable (features and the twelve head
+    parameters) when autograd records; the no-grad path keeps two state slots and saves nothing."""
+    _require_cuda(feats, "MatchingNet head")
+    ops.mn_check(episodes, model.n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    plist = matchingnet_params(model)
+    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in plist)):
+        return _MatchingHeadFn.apply(feats, model.n_way, n_support, n_query, episodes, *plist)
+    return ops.matching_forward(_mn_weights(plist), feats.detach(), episodes, model.n_way, n_support, n_query)[0]
+
+
+class _NLLFn(torch.autograd.Function):
+    """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
+
+    @staticmethod
+    def forward(ctx, logp, target, loss_sum):
+        ctx.save_for_backward(target)
+        ctx.shape = tuple(logp.shape)
+        return ops.nll_mean(logp, target, loss_sum)
+
+    @staticmethod
+    def backward(ctx, g):
+        target, = ctx.saved_tensors
+        return ops.nll_mean_backward(target, ctx.shape[0], ctx.shape[1], g.contiguous().float()), None, None
+
+
+class NLLLoss(torch.nn.NLLLoss):
+    """``nn.NLLLoss()`` as MatchingNet uses it (default arguments, [rows, C] float log-probabilities against [rows] class indices),
+    computed by the HIP library; anything else raises.  ``loss_sum`` as CrossEntropyLoss.loss_sum: the float64 device scalar every
+    forward adds its loss to."""
+
+    loss_sum = CrossEntropyLoss.loss_sum
+
+    def forward(self, input, target):
+        if (self.weight is not None or self.reduction != "mean" or self.ignore_index != -100 or input.dim() != 2 or target.dim() != 1
+                or target.dtype not in (torch.int64, torch.int32) or target.shape[0] != input.shape[0]):
+            raise NotImplementedError("NLLLoss on the HIP path: default options, [rows, C] log-probabilities, [rows] int64 / int32 labels")
+        _require_cuda(input, "NLLLoss")
+        if not target.is_cuda:
+            raise RuntimeError("NLLLoss: labels are on the CPU -- the MI355X path has no CPU fallback; call .cuda() first")
+        if input.dtype != torch.float32 or input.stride(1) != 1:
+            input = input.float().contiguous()
+        return _NLLFn.apply(input, target.contiguous(), self.loss_sum(input.device))

@@ -290,8 +290,11 @@ class FinetuneEngine:
         "proto": finetune.finetune with a ProtoNet model -- the inner loop of "gnn" unchanged, scores = softmax of the ProtoNet
         head on the final-pass features (mft_proto_scores with its softmax epilogue; ``state`` needs only 'feature.*');
         "dist": "linear" with a per-episode Baseline++ head distLinear(512, n_way) in place of the Linear one (one
-        mft_dist_head_step launch per step; scores = one grouped mft_dist_linear_forward launch with its softmax epilogue)."""
-        assert mode in ("gnn", "linear", "proto", "dist")
+        mft_dist_head_step launch per step; scores = one grouped mft_dist_linear_forward launch with its softmax epilogue);
+        "matching": finetune.finetune with a MatchingNet model -- the inner loop of "gnn" unchanged, scores = row softmax of the
+        log-probabilities of the MatchingNet head (ops.matching_forward, all E episodes per launch) on the final-pass features;
+        ``head_state`` holds the twelve FCE.lstmcell.* / G_encoder.* tensors (ops.MN_KEYS)."""
+        assert mode in ("gnn", "linear", "proto", "dist", "matching")
         self.mode = mode
         self.views = mode not in ("linear", "dist")      # the inner loop trains on every view (finetune()); "linear" / "dist" on view 0 only
         # ``graph``: capture one inner step (single stream) as a hipGraph and replay it for every step -- ~40 launches
@@ -353,6 +356,10 @@ class FinetuneEngine:
         # loop's groups are `batch_size` images) -- the fp16 range proof of the f16x2 trunk is made for that size
         self.W = Fn.ResNet10Weights(fsd, self.dev, x3=x3, max_rows=Fn.stem_rows_bound(max(self.n_all, batch_size), image_size))
         self.G = Fn.GnnHeadWeights(head_state if head_state is not None else state, self.dev, n_way) if mode == "gnn" else None
+        if mode == "matching":
+            ops.mn_check(self.E, n_way, n_support, n_query)
+            src = head_state if head_state is not None else state
+            self.MN = {k: src[k].detach().to(self.dev, torch.float32).contiguous().clone() for k in ops.MN_KEYS}
         if mode == "linear":
             self.cls = {k: torch.zeros((self.E, n_way, 512) if k.endswith("W") else (self.E, n_way), device=self.dev)
                         for k in ("W", "b", "mW", "vW", "mb", "vb")}
@@ -757,6 +764,10 @@ class FinetuneEngine:
             # (a fresh tensor, as softmax_rows gives the gnn path: a deferred final pass must not overwrite the previous batch's)
             sc = ops.proto_scores(feats, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
             return sc.view(self.E, self.n_way * self.n_query, self.n_way), feats
+        if self.mode == "matching":
+            # what the reference's finetune() applies to whatever set_forward returns: a row softmax (here of log-probabilities)
+            logp, _ = ops.matching_forward(self.MN, feats, self.E, self.n_way, self.n_support, self.n_query)
+            return ops.softmax_rows(logp).view(self.E, self.n_way * self.n_query, self.n_way), feats
         ns = self.n_support // 2 if self.fold50 else self.n_support
         scores = Fn.gnnnet_scores(self.G, feats, self.E, self.n_way, ns, self.n_query, arena, fold=self.fold50)
         return ops.softmax_rows(scores).view(self.E, self.n_way * self.n_query, self.n_way), feats

@@ -100,7 +100,8 @@ def _head_key(model):
 
 def _engine_for(state_in, model, n_way, n_support, n_query, size, n_views, epochs, E, fold50=False):
     """The finetune() engine for ``model``: a ProtoNet scores with its prototype head (mode "proto": no head weights, the key
-    says so), anything else with the GNN head of its fc / gnn modules."""
+    says so), a MatchingNet with its LSTM / attention head (mode "matching", keyed on the head parameters), anything else with the
+    GNN head of its fc / gnn modules."""
     from .methods.protonet import ProtoNet
     if isinstance(model, ProtoNet):
         cfg = ("proto", n_way, n_support, n_query, size, n_views, epochs, E)
@@ -109,6 +110,18 @@ def _engine_for(state_in, model, n_way, n_support, n_query, size, n_views, epoch
             return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
                                       episodes_per_batch=E, mode="proto")
         return _ENGINES.get(state_in, cfg, build_proto)
+    from .methods.matchingnet import MatchingNet
+    if isinstance(model, MatchingNet):
+        from . import autograd_ops as AG
+        from . import ops
+        plist = AG.matchingnet_params(model)
+        cfg = ("matching", tuple((p.data_ptr(), p._version) for p in plist), n_way, n_support, n_query, size, n_views, epochs, E)
+
+        def build_matching():
+            head = {k: p.detach() for k, p in zip(ops.MN_KEYS, plist)}
+            return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
+                                      episodes_per_batch=E, mode="matching", head_state=head)
+        return _ENGINES.get(state_in, cfg, build_matching)
     cfg = ("gnn", _head_key(model), n_way, n_support, n_query, size, n_views, epochs, E, fold50)
 
     def build():
@@ -302,7 +315,7 @@ def draw_episode_perms(method, n_way, n_support, n_views, fine_tune_epoch, rng=n
     lin = gnn = None
     if method in ("all", "baseline", "baseline++"):          # (finetune_dist is finetune_linear's loop: the same 20 draws)
         lin = [rng.permutation(n_way * n_support) for _ in range(LINEAR_EPOCHS)]
-    if method in ("all", "gnnnet", "protonet"):
+    if method in ("all", "gnnnet", "protonet", "matchingnet"):
         gnn = [rng.permutation(n_way * n_support * (n_views + 1)) for _ in range(fine_tune_epoch)]
     return lin, gnn
 
@@ -451,7 +464,7 @@ def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch,
         s_lin = finetune_linear_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, classifiers=classifiers)
     if method == "baseline++":
         s_lin = finetune_dist_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, heads=classifiers)
-    if method in ("all", "gnnnet", "protonet"):
+    if method in ("all", "gnnnet", "protonet", "matchingnet"):
         s_gnn = finetune_batched(episodes, model, state_gnn, fine_tune_epoch, n_way, n_support, episodes_per_batch, perms=gnn_p)
     if parts:
         return s_lin, s_gnn
@@ -630,7 +643,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             return
         ids = batches[bi]
         if sampler is not None:
-            pipe = (method in ("gnnnet", "protonet") and not freeze_backbone and model is not None)
+            pipe = (method in ("gnnnet", "protonet", "matchingnet") and not freeze_backbone and model is not None)
             eps = []
             for i in ids:
                 src, P, _ = sampler.episode(seed0 + i, size, gen_examples)
@@ -665,7 +678,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             ev.record()
         gens[bi] = (eps, ev, bad)
 
-    pipelined = (method in ("gnnnet", "protonet") and not freeze_backbone and model is not None)
+    pipelined = (method in ("gnnnet", "protonet", "matchingnet") and not freeze_backbone and model is not None)
     n_views = 2 + gen_examples
     engine = None
     flags, score_chunks = [], []

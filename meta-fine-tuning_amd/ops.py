@@ -1075,3 +1075,229 @@ def gather_rows(src2d, idx_i32, out=None):
     _lib.check(_lib.lib().mft_gather_rows(_p(src2d), _p(idx_i32), _p(out), n, src2d.shape[1], _stream()),
                "mft_gather_rows")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- MatchingNet head (csrc/matchingnet.hip)
+MN_D, MN_MAX_S, MN_MAX_WAY = 512, 256, 32
+MN_KEYS = ("FCE.lstmcell.weight_ih", "FCE.lstmcell.weight_hh", "FCE.lstmcell.bias_ih", "FCE.lstmcell.bias_hh",
+           "G_encoder.weight_ih_l0", "G_encoder.weight_hh_l0", "G_encoder.bias_ih_l0", "G_encoder.bias_hh_l0",
+           "G_encoder.weight_ih_l0_reverse", "G_encoder.weight_hh_l0_reverse", "G_encoder.bias_ih_l0_reverse",
+           "G_encoder.bias_hh_l0_reverse")
+
+
+def mn_check(episodes, n_way, n_support, n_query, D=MN_D):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != MN_D:
+        raise ValueError("MatchingNet head: feature dimension %d is not supported (D = %d)" % (D, MN_D))
+    if not 1 <= int(n_way) <= MN_MAX_WAY:
+        raise ValueError("MatchingNet head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), MN_MAX_WAY))
+    if int(n_support) < 1 or int(n_way) * int(n_support) > MN_MAX_S:
+        raise ValueError("MatchingNet head: S = n_way * n_support = %d is not supported (1 <= S <= %d)"
+                         % (int(n_way) * int(n_support), MN_MAX_S))
+    if int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("MatchingNet head: n_query = %d, episodes = %d (both must be >= 1)" % (int(n_query), int(episodes)))
+
+
+def mn_gemm(M, N, a1, lda1, b1, ldb1, K1, c, ldc, ta=False, tb=True, batch=1, a1_bs=0, b1_bs=0, b1_alt=None, a2=None, lda2=0,
+            a2_bs=0, b2=None, ldb2=0, b2_bs=0, K2=0, c_in=None, ldci=0, ci_bs=0, bias1=None, bias2=None, c_bs=0):
+    """mft_mn_gemm: c[z] = c_in[z] + bias1 + bias2 + op(a1[z]) op(b1[z]) + op(a2[z]) op(b2[z]); tensors are passed for their
+    addresses only (views carry the offsets), shapes and strides are the integer arguments."""
+    rc = _lib.lib().mft_mn_gemm(1 if ta else 0, 1 if tb else 0, M, N, batch, _p(a1), lda1, a1_bs, _p(b1), _p(b1_alt), ldb1, b1_bs, K1,
+                                _p(a2), lda2, a2_bs, _p(b2), ldb2, b2_bs, K2, _p(c_in), ldci, ci_bs, _p(bias1), _p(bias2), _p(c),
+                                ldc, c_bs, _stream())
+    _lib.check(rc, "mft_mn_gemm")
+    return c
+
+
+def lstm_step_forward(gates, ld_g, c_prev, ld_cp, f_add, c_out, h_out, ld_o, rows, batch=1, bs_g=0, bs_cp=0, bs_o=0):
+    rc = _lib.lib().mft_lstm_step_forward(_p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(f_add), MN_D, _p(c_out), _p(h_out), ld_o,
+                                          bs_o, rows, MN_D, batch, _stream())
+    _lib.check(rc, "mft_lstm_step_forward")
+
+
+def lstm_step_backward(gates, ld_g, c_prev, ld_cp, c_new, ld_cn, dh1, ld_d1, dh2, ld_d2, dc_in, dc_out, ld_dc, rows, batch=1,
+                       bs_g=0, bs_cp=0, bs_cn=0, bs_d1=0, bs_d2=0, bs_dc=0, dh_sum=None, dgate_sum=None, accumulate=False):
+    rc = _lib.lib().mft_lstm_step_backward(_p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(c_new), ld_cn, bs_cn, _p(dh1), ld_d1,
+                                           bs_d1, _p(dh2), ld_d2, bs_d2, _p(dc_in), _p(dc_out), ld_dc, bs_dc, _p(dh_sum),
+                                           _p(dgate_sum), 1 if accumulate else 0, rows, MN_D, batch, _stream())
+    _lib.check(rc, "mft_lstm_step_backward")
+
+
+def mn_attention_forward(h, G, episodes, Q, S, a, r):
+    _lib.check(_lib.lib().mft_mn_attention_forward(_p(h), _p(G), episodes, Q, S, MN_D, _p(a), _p(r), _stream()),
+               "mft_mn_attention_forward")
+
+
+def mn_attention_backward(dr, a, G, dh_in, episodes, Q, S, dlogit, dh_out):
+    _lib.check(_lib.lib().mft_mn_attention_backward(_p(dr), _p(a), _p(G), _p(dh_in), episodes, Q, S, MN_D, _p(dlogit), _p(dh_out),
+                                                    _stream()), "mft_mn_attention_backward")
+
+
+def mn_readout_forward(h, G, gnorm, episodes, n_way, n_support, n_query):
+    """-> dict(cos, p [M, S], hnorm [M], pc, logp [M, n_way]) for h [M = episodes * n_way * n_query, D], G [episodes, S, D]."""
+    mn_check(episodes, n_way, n_support, n_query, h.shape[-1])
+    M, S = episodes * n_way * n_query, n_way * n_support
+    new = lambda *s: torch.empty(s, device=h.device, dtype=torch.float32)  # noqa: E731
+    o = {"cos": new(M, S), "p": new(M, S), "hnorm": new(M), "pc": new(M, n_way), "logp": new(M, n_way)}
+    rc = _lib.lib().mft_mn_readout_forward(_p(h), _p(G), _p(gnorm), episodes, n_way, n_support, n_query, MN_D, _p(o["cos"]), _p(o["p"]),
+                                           _p(o["hnorm"]), _p(o["pc"]), _p(o["logp"]), _stream())
+    _lib.check(rc, "mft_mn_readout_forward")
+    return o
+
+
+def mn_readout_backward(dlogp, h, G, gnorm, ro, episodes, n_way, n_support, n_query):
+    """-> (dh [M, D], dG [episodes, S, D]) from d(logp) [M, n_way] and the forward's dict."""
+    M, S = episodes * n_way * n_query, n_way * n_support
+    new = lambda *s: torch.empty(s, device=h.device, dtype=torch.float32)  # noqa: E731
+    dcos, dh, dG = new(M, S), new(M, MN_D), new(episodes, S, MN_D)
+    rc = _lib.lib().mft_mn_readout_backward(_p(dlogp), dlogp.stride(0), _p(h), _p(G), _p(gnorm), _p(ro["cos"]), _p(ro["p"]),
+                                            _p(ro["hnorm"]), _p(ro["pc"]), episodes, n_way, n_support, n_query, MN_D, _p(dcos), _p(dh),
+                                            _p(dG), _stream())
+    _lib.check(rc, "mft_mn_readout_backward")
+    return dh, dG
+
+
+def mn_colsum(x, rows, C, out=None):
+    out = torch.empty(C, device=x.device, dtype=torch.float32) if out is None else out
+    _lib.check(_lib.lib().mft_mn_colsum(_p(x), C, C, rows, _p(out), _stream()), "mft_mn_colsum")
+    return out
+
+
+def nll_mean(logp, target, loss_sum=None):
+    rows, C = logp.shape
+    loss = torch.empty((), device=logp.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mft_nll_mean(_p(logp), logp.stride(0), _p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(loss),
+                                       _p(loss_sum), _stream()), "mft_nll_mean")
+    return loss
+
+
+def nll_mean_backward(target, rows, C, g):
+    d = torch.empty((rows, C), device=target.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mft_nll_mean_backward(_p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(g), _p(d), C,
+                                                _stream()), "mft_nll_mean_backward")
+    return d
+
+
+def mn_encoder_forward(W, zS, E, S):
+    """G_encoder over every episode's support sequence, both directions in lockstep: -> (eg, eh, ec) [2, E, S, 4D | D | D], the gate
+    activations, hidden and cell states of every step (direction 1 runs the rows backwards)."""
+    D = MN_D
+    new = lambda *s: torch.empty(s, device=zS.device, dtype=torch.float32)  # noqa: E731
+    eg, eh, ec = new(2, E, S, 4 * D), new(2, E, S, D), new(2, E, S, D)
+    for d, sfx in enumerate(("", "_reverse")):          # input parts of all S steps at once
+        mn_gemm(E * S, 4 * D, zS, D, W["G_encoder.weight_ih_l0" + sfx], D, D, eg[d], 4 * D,
+                bias1=W["G_encoder.bias_ih_l0" + sfx], bias2=W["G_encoder.bias_hh_l0" + sfx])
+    for t in range(S):
+        r0, r1 = t, S - 1 - t                           # the row each direction writes at step t
+        if t > 0:
+            p0, p1 = r0 - 1, r1 + 1                     # ... and the row that holds its previous state
+            mn_gemm(E, 4 * D, eh[0, :, p0], S * D, W["G_encoder.weight_hh_l0"], D, D, eg[0, :, r0], S * 4 * D, batch=2,
+                    a1_bs=(E * S + p1 - p0) * D, b1_alt=W["G_encoder.weight_hh_l0_reverse"], c_in=eg[0, :, r0], ldci=S * 4 * D,
+                    ci_bs=(E * S + r1 - r0) * 4 * D, c_bs=(E * S + r1 - r0) * 4 * D)
+        lstm_step_forward(eg[0, :, r0], S * 4 * D, ec[0, :, p0] if t > 0 else None, S * D, None, ec[0, :, r0], eh[0, :, r0], S * D, E,
+                          batch=2, bs_g=(E * S + r1 - r0) * 4 * D, bs_cp=(E * S + p1 - p0) * D if t > 0 else 0,
+                          bs_o=(E * S + r1 - r0) * D)
+    return eg, eh, ec
+
+
+def matching_forward(W, feats, episodes, n_way, n_support, n_query, save=False):
+    """MatchingNet head forward: feats [episodes * n_way * (n_support + n_query), 512] (class-major rows, one
+    episode after the other), W: the twelve head parameters by state-dict key (MN_KEYS) -> (logp [episodes * n_way * n_query,
+    n_way], tape | None).  ``save``: keep the per-step h, c, a, r and gates for matching_backward (S + 1 slots instead of 2)."""
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("MatchingNet head: expected float32 rows [R, D] with unit column stride, got %s %s" % (feats.dtype, tuple(feats.shape)))
+    mn_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    E, D, S, Q = episodes, MN_D, n_way * n_support, n_way * n_query
+    M = E * Q
+    if feats.shape[0] != E * n_way * (n_support + n_query):
+        raise ValueError("MatchingNet head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]"
+                         % (tuple(feats.shape), E * n_way * (n_support + n_query), D))
+    new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
+    T = S + 1 if save else 2
+    Tg = S if save else 1
+    zS, f, fh, fc = new(E, S, D), new(M, D), new(T, M, D), new(T, M, D)
+    _lib.check(_lib.lib().mft_mn_gather(_p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(zS), _p(f), _p(fh[0]), _stream()),
+               "mft_mn_gather")
+    eg, eh, ec = mn_encoder_forward(W, zS, E, S)
+    G, gnorm = new(E, S, D), new(E, S)
+    _lib.check(_lib.lib().mft_mn_encode_combine(_p(zS), _p(eh[0]), _p(eh[1]), E, S, D, _p(G), _p(gnorm), _stream()), "mft_mn_encode_combine")
+    # FCE: the f half of the cell's input part does not change over the S steps
+    wih, whh = W["FCE.lstmcell.weight_ih"], W["FCE.lstmcell.weight_hh"]
+    Pf = mn_gemm(M, 4 * D, f, D, wih, 2 * D, D, new(M, 4 * D), 4 * D, bias1=W["FCE.lstmcell.bias_ih"], bias2=W["FCE.lstmcell.bias_hh"])
+    fg, fa, fr = new(Tg, M, 4 * D), new(Tg, M, S), new(Tg, M, D)
+    wih_r = wih[:, D:]
+    for k in range(S):
+        si, so, sg = k % T, (k + 1) % T, k % Tg
+        mn_attention_forward(fh[si], G, E, Q, S, fa[sg], fr[sg])
+        mn_gemm(M, 4 * D, fh[si], D, whh, D, D, fg[sg], 4 * D, a2=fr[sg], lda2=D, b2=wih_r, ldb2=2 * D, K2=D, c_in=Pf, ldci=4 * D)
+        lstm_step_forward(fg[sg], 4 * D, fc[si] if k > 0 else None, D, f, fc[so], fh[so], D, M)
+    hS = fh[S % T]
+    ro = mn_readout_forward(hS, G, gnorm, E, n_way, n_support, n_query)
+    if not save:
+        return ro["logp"], None
+    tape = dict(zS=zS, f=f, fh=fh, fc=fc, eg=eg, eh=eh, ec=ec, G=G, gnorm=gnorm, fg=fg, fa=fa, fr=fr, ro=ro,
+                shape=(E, n_way, n_support, n_query))
+    return ro["logp"], tape
+
+
+def matching_backward(W, tape, dlogp):
+    """d(logp) [M, n_way] -> (dfeats [episodes * n_way * (n_support + n_query), 512], {state-dict key: gradient}).  Consumes the tape:
+    the saved gates are overwritten by d(pre-activations), and every weight gradient is ONE transposed GEMM over all steps."""
+    E, n_way, n_support, n_query = tape["shape"]
+    D, S, Q = MN_D, n_way * n_support, n_way * n_query
+    M = E * Q
+    zS, f, fh, fc, eg, eh, ec, G, fg, fa, fr = (tape[k] for k in ("zS", "f", "fh", "fc", "eg", "eh", "ec", "G", "fg", "fa", "fr"))
+    new = lambda *s: torch.empty(s, device=zS.device, dtype=torch.float32)  # noqa: E731
+    wih, whh = W["FCE.lstmcell.weight_ih"], W["FCE.lstmcell.weight_hh"]
+    wih_r = wih[:, D:]
+    g = {}
+    dh, dG = mn_readout_backward(dlogp, fh[S], G, tape["gnorm"], tape["ro"], E, n_way, n_support, n_query)
+    # ---- FCE, last step first
+    dc, df, dPf, dhl, dr, dlogit, dh2 = new(M, D), new(M, D), new(M, 4 * D), new(M, D), new(M, D), new(M, S), new(M, D)
+    for k in range(S - 1, -1, -1):
+        first = k == S - 1
+        lstm_step_backward(fg[k], 4 * D, fc[k] if k > 0 else None, D, fc[k + 1], D, dh, D, None, 0, None if first else dc, dc, D, M,
+                           dh_sum=df, dgate_sum=dPf, accumulate=not first)
+        mn_gemm(M, D, fg[k], 4 * D, whh, D, 4 * D, dhl, D, tb=False)
+        mn_gemm(M, D, fg[k], 4 * D, wih_r, 2 * D, 4 * D, dr, D, tb=False)
+        mn_attention_backward(dr, fa[k], G, dhl, E, Q, S, dlogit, dh2)
+        mn_gemm(S, D, fa[k], S, dr, D, Q, dG, D, ta=True, tb=False, batch=E, a1_bs=Q * S, b1_bs=Q * D, a2=dlogit, lda2=S,
+                a2_bs=Q * S, b2=fh[k], ldb2=D, b2_bs=Q * D, K2=Q, c_in=dG, ldci=D, ci_bs=S * D, c_bs=S * D)
+        dh, dh2 = dh2, dh
+    mn_gemm(M, D, dPf, 4 * D, wih, 2 * D, 4 * D, df, D, tb=False, c_in=df, ldci=D)        # df += dPf W_ih[:, :D]; dh is d(h_0 = f)
+    gw = new(4 * D, 2 * D)
+    mn_gemm(4 * D, D, dPf, 4 * D, f, D, M, gw, 2 * D, ta=True, tb=False)
+    mn_gemm(4 * D, D, fg, 4 * D, fr, D, S * M, gw[:, D:], 2 * D, ta=True, tb=False)
+    g["FCE.lstmcell.weight_ih"] = gw
+    g["FCE.lstmcell.weight_hh"] = mn_gemm(4 * D, D, fg, 4 * D, fh, D, S * M, new(4 * D, D), D, ta=True, tb=False)
+    g["FCE.lstmcell.bias_ih"] = mn_colsum(dPf, M, 4 * D)
+    g["FCE.lstmcell.bias_hh"] = mn_colsum(dPf, M, 4 * D)
+    # ---- G_encoder: d(out_forward) = d(out_reverse) = d(z_S, direct) = dG; direction 0 walks its rows backwards, direction 1 forwards
+    edc, edh = new(2, E, D), new(2, E, D)
+    for u in range(S):
+        r0, r1 = S - 1 - u, u
+        more = u < S - 1
+        bs = E * S + r1 - r0
+        lstm_step_backward(eg[0, :, r0], S * 4 * D, ec[0, :, r0 - 1] if more else None, S * D, ec[0, :, r0], S * D, dG[:, r0], S * D,
+                           edh if u > 0 else None, D, edc if u > 0 else None, edc, D, E, batch=2, bs_g=bs * 4 * D,
+                           bs_cp=(bs + 2) * D, bs_cn=bs * D, bs_d1=(r1 - r0) * D, bs_d2=E * D, bs_dc=E * D)
+        if more:
+            mn_gemm(E, D, eg[0, :, r0], S * 4 * D, W["G_encoder.weight_hh_l0"], D, 4 * D, edh, D, tb=False, batch=2, a1_bs=bs * 4 * D,
+                    b1_alt=W["G_encoder.weight_hh_l0_reverse"], c_bs=E * D)
+    dzS = mn_gemm(E * S, D, eg[0], 4 * D, W["G_encoder.weight_ih_l0"], D, 4 * D, new(E, S, D), D, tb=False, a2=eg[1], lda2=4 * D,
+                  b2=W["G_encoder.weight_ih_l0_reverse"], ldb2=D, K2=4 * D, c_in=dG, ldci=D)
+    for d, sfx in enumerate(("", "_reverse")):
+        g["G_encoder.weight_ih_l0" + sfx] = mn_gemm(4 * D, D, eg[d], 4 * D, zS, D, E * S, new(4 * D, D), D, ta=True, tb=False)
+        gh = new(4 * D, D)
+        for e in range(E):          # the state a step reads sits one row before (direction 0) / after (direction 1) its own
+            a, b = (eg[d, e, 1:], eh[d, e]) if d == 0 else (eg[d, e], eh[d, e, 1:])
+            mn_gemm(4 * D, D, a if S > 1 else eg[d, e], 4 * D, b if S > 1 else eh[d, e], D, S - 1, gh, D, ta=True, tb=False,
+                    c_in=gh if e > 0 else None, ldci=D)
+        g["G_encoder.weight_hh_l0" + sfx] = gh
+        g["G_encoder.bias_ih_l0" + sfx] = mn_colsum(eg[d], E * S, 4 * D)
+        g["G_encoder.bias_hh_l0" + sfx] = mn_colsum(eg[d], E * S, 4 * D)
+    per = n_way * (n_support + n_query)
+    dfeats = new(E * per, D)
+    _lib.check(_lib.lib().mft_mn_scatter_backward(_p(dzS), _p(df), _p(dh), E, n_way, n_support, n_query, D, _p(dfeats), D, _stream()),
+               "mft_mn_scatter_backward")
+    return dfeats, g

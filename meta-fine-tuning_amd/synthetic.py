@@ -122,6 +122,19 @@ def gnnnet_state_dict_with_running_stats(seed=0, n_way=5):
 
 # ----------------------------------------------------------------------------- episodes
 
+def matchingnet_head_state(seed=26, dim=512):
+    """The twelve MatchingNet head tensors as torch initialises them right after ``torch.manual_seed(seed)``:
+    nn.LSTMCell(2 * dim, dim) first, then nn.LSTM(dim, dim, 1, batch_first=True, bidirectional=True); state-dict keys and order
+    of methods.matchingnet.MatchingNet after ``feature.*``.  The global torch RNG is left as it was."""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        cell = torch.nn.LSTMCell(2 * dim, dim)
+        enc = torch.nn.LSTM(dim, dim, 1, batch_first=True, bidirectional=True)
+    sd = OrderedDict(("FCE.lstmcell." + k, v.detach().clone()) for k, v in cell.state_dict().items())
+    sd.update(("G_encoder." + k, v.detach().clone()) for k, v in enc.state_dict().items())
+    return sd
+
+
 def _templates(rs, n_way, size):
     """Per-class low-frequency templates: 7x7 gaussian grids upsampled bilinearly."""
     low = torch.from_numpy(rs.standard_normal((n_way, 3, 7, 7)).astype(np.float32))
