@@ -524,6 +524,33 @@ int mft_nll_mean(const float* logp, int ld, const void* labels, int labels_i64, 
 int mft_nll_mean_backward(const void* labels, int labels_i64, int C, int rows, const float* grad_loss, float* dlogp, int ldd,
                           void* stream);
 
+/* MetaOptNet ridge-regression head (csrc/ridge.hip), every episode of a step per launch.  feats as for
+ * mft_proto_scores (D = 512); support row s of an episode is class s / n_support, S = n_way * n_support; the one-hot Y is
+ * computed from the row index.  Storage fp32, sums in double inside the kernels, fixed summation order, no atomics.
+ *   gram:          A [episodes, S, S] (lower triangle only) = Z_S Z_S^T + lambda_reg I
+ *   factor_solve:  A -> its Cholesky factor L in place (lower triangle); alpha [episodes, S, n_way] = 2 A^-1 Y;
+ *                  W [episodes, n_way, D] (one row per class) = (Z_S^T alpha)^T.  One workgroup per episode.
+ *   scores:        scores [episodes * n_way * n_query, n_way] = scale[0] * Z_Q W (scale a DEVICE scalar); softmax = 1: their row
+ *                  softmax instead.
+ *   backward_query:   G = dscores (row stride ldg >= n_way): dfeats query rows = scale G W^T, dW [episodes, n_way, D] = scale
+ *                  (Z_Q^T G)^T, dscale_part [episodes * 8] (float64) = the shares of sum(G * (Z_Q W)).
+ *   backward_support: dalpha = Z_S dW^T, B = A^-1 dalpha from the saved L, dfeats support rows = alpha dW - B W - alpha (Z_S^T
+ *                  B)^T; dscale[0] = the sum of dscale_part in index order.  Together the two write EVERY row of dfeats.
+ * MFT_EINVAL outside n_way 1..32, S 1..256, n_query >= 1, episodes >= 1, D = 512, ld >= D a multiple of 4 (ldd >= D), 16-byte
+ * aligned feats / W / dW. */
+int mft_ridge_gram(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, float lambda_reg,
+                   float* A, void* stream);
+int mft_ridge_factor_solve(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, float* A,
+                           float* alpha, float* W, void* stream);
+int mft_ridge_scores(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* W,
+                     const float* scale, float* scores, int softmax, void* stream);
+int mft_ridge_backward_query(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
+                             const float* W, const float* scale, const float* dscores, int ldg, float* dfeats, int ldd, float* dW,
+                             double* dscale_part, void* stream);
+int mft_ridge_backward_support(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
+                               const float* L, const float* alpha, const float* W, const float* dW, const double* dscale_part,
+                               float* dfeats, int ldd, float* dscale, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

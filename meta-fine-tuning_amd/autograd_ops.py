@@ -442,6 +442,43 @@ def matchingnet_head(model, feats, n_support, n_query, episodes=1):
     return ops.matching_forward(_mn_weights(plist), feats.detach(), episodes, model.n_way, n_support, n_query)[0]
 
 
+class _RidgeHeadFn(torch.autograd.Function):
+    """MetaOptNet ridge-regression head with a hand-written backward: ops.ridge_forward keeps the Cholesky
+    factor, alpha and W, ops.ridge_backward returns the gradients of every feature row and of ``scale``."""
+
+    @staticmethod
+    def forward(ctx, feats, scale, n_way, n_support, n_query, episodes):
+        scores, tape = ops.ridge_forward(feats, scale.detach(), episodes, n_way, n_support, n_query, save=True)
+        tape.pop("feats")
+        tape.pop("scale")
+        ctx.save_for_backward(feats, scale)
+        ctx.tape = tape
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, scale = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.stride(1) == 1) else dscores.contiguous().float()
+        dfeats, dscale = ops.ridge_backward(dict(ctx.tape, feats=feats, scale=scale.detach()), d)
+        return (dfeats if ctx.needs_input_grad[0] else None, dscale.view(scale.shape) if ctx.needs_input_grad[1] else None,
+                None, None, None, None)
+
+
+def metaoptnet_head(feats, scale, n_way, n_support, n_query, episodes=1):
+    """MetaOptNet.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one
+    episode after the other), scale the head's one-element parameter -> scores [episodes*n_way*n_query, n_way] = scale * Z_Q W of
+    the ridge regression on the support rows.  Differentiable (features and scale) when autograd records; the no-grad path saves
+    nothing."""
+    _require_cuda(feats, "MetaOptNet head")
+    _require_cuda(scale, "MetaOptNet head")
+    ops.ridge_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and (feats.requires_grad or scale.requires_grad):
+        return _RidgeHeadFn.apply(feats, scale, n_way, n_support, n_query, episodes)
+    return ops.ridge_forward(feats.detach(), scale.detach(), episodes, n_way, n_support, n_query)[0]
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

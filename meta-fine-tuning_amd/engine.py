@@ -293,8 +293,11 @@ class FinetuneEngine:
         mft_dist_head_step launch per step; scores = one grouped mft_dist_linear_forward launch with its softmax epilogue);
         "matching": finetune.finetune with a MatchingNet model -- the inner loop of "gnn" unchanged, scores = row softmax of the
         log-probabilities of the MatchingNet head (ops.matching_forward, all E episodes per launch) on the final-pass features;
-        ``head_state`` holds the twelve FCE.lstmcell.* / G_encoder.* tensors (ops.MN_KEYS)."""
-        assert mode in ("gnn", "linear", "proto", "dist", "matching")
+        ``head_state`` holds the twelve FCE.lstmcell.* / G_encoder.* tensors (ops.MN_KEYS).
+        "ridge": finetune.finetune with a MetaOptNet model -- the inner loop of "gnn" unchanged, scores = the ridge-regression head
+        (ops.ridge_forward with its softmax epilogue, all E episodes per launch) on the final-pass features; ``head_state`` holds
+        ``scale``."""
+        assert mode in ("gnn", "linear", "proto", "dist", "matching", "ridge")
         self.mode = mode
         self.views = mode not in ("linear", "dist")      # the inner loop trains on every view (finetune()); "linear" / "dist" on view 0 only
         # ``graph``: capture one inner step (single stream) as a hipGraph and replay it for every step -- ~40 launches
@@ -360,6 +363,10 @@ class FinetuneEngine:
             ops.mn_check(self.E, n_way, n_support, n_query)
             src = head_state if head_state is not None else state
             self.MN = {k: src[k].detach().to(self.dev, torch.float32).contiguous().clone() for k in ops.MN_KEYS}
+        if mode == "ridge":
+            ops.ridge_check(self.E, n_way, n_support, n_query)
+            src = head_state if head_state is not None else state
+            self.ridge_scale = src["scale"].detach().to(self.dev, torch.float32).reshape(1).clone()
         if mode == "linear":
             self.cls = {k: torch.zeros((self.E, n_way, 512) if k.endswith("W") else (self.E, n_way), device=self.dev)
                         for k in ("W", "b", "mW", "vW", "mb", "vb")}
@@ -768,6 +775,9 @@ class FinetuneEngine:
             # what the reference's finetune() applies to whatever set_forward returns: a row softmax (here of log-probabilities)
             logp, _ = ops.matching_forward(self.MN, feats, self.E, self.n_way, self.n_support, self.n_query)
             return ops.softmax_rows(logp).view(self.E, self.n_way * self.n_query, self.n_way), feats
+        if self.mode == "ridge":
+            sc, _ = ops.ridge_forward(feats, self.ridge_scale, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
+            return sc.view(self.E, self.n_way * self.n_query, self.n_way), feats
         ns = self.n_support // 2 if self.fold50 else self.n_support
         scores = Fn.gnnnet_scores(self.G, feats, self.E, self.n_way, ns, self.n_query, arena, fold=self.fold50)
         return ops.softmax_rows(scores).view(self.E, self.n_way * self.n_query, self.n_way), feats

@@ -16,7 +16,7 @@ _COMMON = [
     ("--test_dataset", dict(default="", help="test dataset")),
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
-    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/gnnnet/all")),
+    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/gnnnet/all")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),
     ("--test_n_way", dict(default=5, type=int, help="class num to classify for testing (validation)")),
     ("--n_shot", dict(default=5, type=int, help="number of labeled data in each class, same as n_support")),
@@ -36,7 +36,7 @@ _PER_SCRIPT = {
         ("--start_epoch", dict(default=0, type=int, help="Starting epoch")),
         ("--stop_epoch", dict(default=400, type=int, help="Stopping epoch")),
         # (not in the reference: k episodes per optimizer step in lockstep on one GPU = the update of a k-rank episode-parallel run)
-        ("--episodes_per_rank", dict(default=1, type=int, help="gnnnet / protonet / matchingnet without --fine_tune: episodes per optimizer step (lockstep)")),
+        ("--episodes_per_rank", dict(default=1, type=int, help="gnnnet / protonet / matchingnet / metaoptnet without --fine_tune: episodes per optimizer step (lockstep)")),
     ],
     "save_features": [("--split", dict(default="novel", help="base/val/novel"))],
     "test": [

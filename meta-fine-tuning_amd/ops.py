@@ -1301,3 +1301,85 @@ def matching_backward(W, tape, dlogp):
     _lib.check(_lib.lib().mft_mn_scatter_backward(_p(dzS), _p(df), _p(dh), E, n_way, n_support, n_query, D, _p(dfeats), D, _stream()),
                "mft_mn_scatter_backward")
     return dfeats, g
+
+
+# ---------------------------------------------------------------------------------------------- MetaOptNet ridge head (csrc/ridge.hip)
+RIDGE_D, RIDGE_MAX_S, RIDGE_MAX_WAY = 512, 256, 32
+RIDGE_LAMBDA = 50.0
+
+
+def ridge_check(episodes, n_way, n_support, n_query, D=RIDGE_D):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != RIDGE_D:
+        raise ValueError("MetaOptNet head: feature dimension %d is not supported (D = %d)" % (D, RIDGE_D))
+    if not 1 <= int(n_way) <= RIDGE_MAX_WAY:
+        raise ValueError("MetaOptNet head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), RIDGE_MAX_WAY))
+    if int(n_support) < 1 or int(n_way) * int(n_support) > RIDGE_MAX_S:
+        raise ValueError("MetaOptNet head: S = n_way * n_support = %d is not supported (1 <= S <= %d)"
+                         % (int(n_way) * int(n_support), RIDGE_MAX_S))
+    if int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("MetaOptNet head: n_query = %d, episodes = %d (both must be >= 1)" % (int(n_query), int(episodes)))
+
+
+def _ridge_feats(feats, episodes, n_way, n_support, n_query):
+    if not feats.is_cuda:
+        raise RuntimeError("MetaOptNet head: input is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % feats.device)
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("MetaOptNet head: expected float32 rows [R, D] with unit column stride, got %s %s" % (feats.dtype, tuple(feats.shape)))
+    ridge_check(episodes, n_way, n_support, n_query, feats.shape[1])
+    if feats.shape[0] != episodes * n_way * (n_support + n_query):
+        raise ValueError("MetaOptNet head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]"
+                         % (tuple(feats.shape), episodes * n_way * (n_support + n_query), RIDGE_D))
+    if feats.stride(0) < RIDGE_D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("MetaOptNet head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), RIDGE_D))
+
+
+def _ridge_scale(scale):
+    if not torch.is_tensor(scale) or not scale.is_cuda or scale.dtype != torch.float32 or scale.numel() != 1:
+        raise RuntimeError("MetaOptNet head: scale must be a one-element float32 tensor on the GPU (no CPU fallback)")
+    return scale
+
+
+def ridge_forward(feats, scale, episodes, n_way, n_support, n_query, softmax=False, save=False, lambda_reg=RIDGE_LAMBDA):
+    """MetaOptNet-RR head forward: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one
+    episode after the other, row stride >= 512), scale a one-element device tensor -> (scores [episodes*n_way*n_query, n_way],
+    tape | None); ``softmax``: the row softmax of the scores instead.  Three launches whatever the shape: Gram matrix, Cholesky
+    factor + alpha + W, scores.  ``save``: keep L, alpha and W for ridge_backward."""
+    _ridge_feats(feats, episodes, n_way, n_support, n_query)
+    _ridge_scale(scale)
+    E, D, S, Q = episodes, RIDGE_D, n_way * n_support, n_way * n_query
+    new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
+    A, alpha, W, scores = new(E, S, S), new(E, S, n_way), new(E, n_way, D), new(E * Q, n_way)
+    h, ld = _lib.lib(), feats.stride(0)
+    _lib.check(h.mft_ridge_gram(_p(feats), ld, E, n_way, n_support, n_query, D, float(lambda_reg), _p(A), _stream()), "mft_ridge_gram")
+    _lib.check(h.mft_ridge_factor_solve(_p(feats), ld, E, n_way, n_support, n_query, D, _p(A), _p(alpha), _p(W), _stream()),
+               "mft_ridge_factor_solve")
+    _lib.check(h.mft_ridge_scores(_p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
+                                  _stream()), "mft_ridge_scores")
+    if not save:
+        return scores, None
+    return scores, dict(feats=feats, scale=scale, L=A, alpha=alpha, W=W, shape=(E, n_way, n_support, n_query))
+
+
+def ridge_backward(tape, dscores):
+    """d(scores) [episodes*n_way*n_query, n_way] -> (dfeats [rows, 512] with every row written, dscale [1]) from the forward's
+    tape.  Two launches whatever the shape: query side (dZ_Q, dW, the shares of dscale), support side (dalpha, B, dZ_S)."""
+    E, n_way, n_support, n_query = tape["shape"]
+    feats, scale = tape["feats"], tape["scale"]
+    D, Q = RIDGE_D, n_way * n_query
+    if not dscores.is_cuda:
+        raise RuntimeError("MetaOptNet head: d(scores) is on %s -- the MI355X path has no CPU fallback" % dscores.device)
+    if dscores.dtype != torch.float32 or dscores.dim() != 2 or dscores.stride(1) != 1:
+        raise RuntimeError("MetaOptNet head: expected float32 d(scores) with unit column stride")
+    if tuple(dscores.shape) != (E * Q, n_way):
+        raise ValueError("ridge_backward: dscores is %s, expected [%d, %d]" % (tuple(dscores.shape), E * Q, n_way))
+    new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
+    dfeats, dW, dscale = new(feats.shape[0], D), new(E, n_way, D), new(1)
+    part = torch.empty(E * 8, device=feats.device, dtype=torch.float64)
+    h, ld = _lib.lib(), feats.stride(0)
+    _lib.check(h.mft_ridge_backward_query(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
+                                          dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream()), "mft_ridge_backward_query")
+    _lib.check(h.mft_ridge_backward_support(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["L"]), _p(tape["alpha"]),
+                                            _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream()),
+               "mft_ridge_backward_support")
+    return dfeats, dscale

@@ -135,6 +135,15 @@ def matchingnet_head_state(seed=26, dim=512):
     return sd
 
 
+def metaoptnet_head_state(seed=27):
+    """The MetaOptNet head's one tensor: ``scale`` [1], drawn from [0.5, 1.5) and never 1 (the module's
+    initial value), so that a test that ignored it would fail."""
+    v = np.random.RandomState(seed).uniform(0.5, 1.5)
+    if abs(v - 1.0) < 0.05:
+        v += 0.25
+    return OrderedDict([("scale", torch.tensor([v], dtype=torch.float32))])
+
+
 def _templates(rs, n_way, size):
     """Per-class low-frequency templates: 7x7 gaussian grids upsampled bilinearly."""
     low = torch.from_numpy(rs.standard_normal((n_way, 3, 7, 7)).astype(np.float32))

@@ -1,4 +1,4 @@
-"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / baseline / baseline++): Adam over all parameters, 100
+"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / baseline / baseline++): Adam over all parameters, 100
 episodes per epoch, checkpoints ``{'epoch','state'}`` under <save_dir>/checkpoints/<dataset>/<model>_<method>
 [_aug]_<n>way_<k>shot/<epoch>.tar, optional first-order-MAML meta-fine-tuning (--fine_tune).
 The episode source is the in-repo synthetic miniImageNet-shaped sampler (real data is out of scope)."""
@@ -12,6 +12,7 @@ from .io_utils import get_assigned_file, model_dict, parse_args
 from .methods import gnnnet_copy
 from .methods.gnnnet import GnnNet
 from .methods.matchingnet import MatchingNet
+from .methods.metaoptnet import MetaOptNet
 from .methods.protonet import ProtoNet
 
 
@@ -187,11 +188,11 @@ def train(base_loader, model, optimization, start_epoch, stop_epoch, params, var
         if params.method in ('baseline', 'baseline++'):
             model.train_loop(epoch, base_loader, optimizer)              # train.py:41-42: every other method -> train_loop
         elif not params.fine_tune and getattr(params, "episodes_per_rank", 1) > 1:
-            if fifty and params.method not in ('protonet', 'matchingnet'):
+            if fifty and params.method not in ('protonet', 'matchingnet', 'metaoptnet'):
                 raise NotImplementedError("--episodes_per_rank with the 50-shot loops")
             model.train_loop_lockstep(epoch, base_loader, optimizer, params.episodes_per_rank)
         elif not params.fine_tune:
-            if params.method in ('protonet', 'matchingnet'):
+            if params.method in ('protonet', 'matchingnet', 'metaoptnet'):
                 model.train_loop(epoch, base_loader, optimizer)          # train.py:48-49 / train_50.py:48-49: the else branch
             else:
                 (model.train_loop50 if fifty else model.train_loop2)(epoch, base_loader, optimizer)
@@ -223,13 +224,15 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     rank, W = parallel.world()
     if not params.start_epoch > 0:
         np.random.seed(10)
-    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'baseline' and 'baseline++' are on the HIP path"
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'baseline' and 'baseline++' are on the HIP path"
                                   % params.method)
     if params.method == 'protonet' and params.fine_tune:
         raise NotImplementedError("--method protonet --fine_tune: ProtoNet's first-order-MAML meta-training is not on the HIP path")
     if params.method == 'matchingnet' and params.fine_tune:
         raise NotImplementedError("--method matchingnet --fine_tune: MatchingNet's first-order-MAML meta-training is not on the HIP path")
+    if params.method == 'metaoptnet' and params.fine_tune:
+        raise NotImplementedError("--method metaoptnet --fine_tune: MetaOptNet's first-order-MAML meta-training is not on the HIP path")
     params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model, params.method)
     if params.train_aug:
         params.checkpoint_dir += '_aug'
@@ -252,6 +255,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
             cls = ProtoNet                                               # train.py:138-139
         elif params.method == 'matchingnet':
             cls = MatchingNet
+        elif params.method == 'metaoptnet':
+            cls = MetaOptNet
         else:
             cls = gnnnet_copy.GnnNet if (variant50 and params.n_shot == 50) else GnnNet          # train_50.py:154-157
         torch.manual_seed(0) if W > 1 else None
