@@ -828,6 +828,33 @@ int mft_build_graph_nodes_backward(const float* dnodes, int ld, float* dz, int z
 int mft_gather_query_scores_backward(const float* dscores, float* dout, int ldo, int n_episodes, int n_way,
                                      int n_support, int n_query, float* dbias, void* stream);
 
+/* Feature-wise transformation layers of ResNet10_FW (backbone.py:313-350): in train mode
+ * y = gm * bn(x) + bt with gm = 1 + n_g * softplus(gamma), bt = n_b * softplus(beta), n_g, n_b ~ N(0, 1) per channel and call --
+ * a BatchNorm with the affine (w', b') = (gm * w, gm * b + bt).  jobs: HOST array of up to 8 layers, passed by value.
+ * Noise layout: [groups, 2, ld] floats, row 0 = n_g, row 1 = n_b, layer l in columns col .. col + C.
+ * Draw + fold, ONE workgroup for every layer and group: normals from Philox4x32-10 (counter = column, group, draw index low / high;
+ * key = seed; words 0, 1 -> Box-Muller in double, rounded once) or, with noise_in != NULL, read from noise_in; writes noise, gm,
+ * w_fold, b_fold [groups, C] (operands of the BatchNorm launchers with gb_group_stride = C) and stores *index + 1 to the DEVICE
+ * counter index.  words (nullable, [groups, 2, ld]): the raw generator words.  MFT_EINVAL outside C <= 512, 1 <= n_layers <= 8,
+ * groups >= 1, col + C <= ld. */
+typedef struct MftFwtJob {
+    const float* w; const float* b; const float* gamma; const float* beta;
+    float* w_fold; float* b_fold; float* gm;
+    int C, col;
+} MftFwtJob;
+int mft_fwt_draw_fold(const MftFwtJob* jobs, int n_layers, int groups, int ld, unsigned long long seed, unsigned long long* index,
+                      const float* noise_in, float* noise, unsigned* words, void* stream);
+/* Unfold: from the BatchNorm backward's per-group gradients dw_fold, db_fold [groups, C] of (w', b'):
+ * dw = sum_g gm_g dw'_g, db = sum_g gm_g db'_g, dgamma = sigmoid(100 gamma) sum_g n_g,g (w dw'_g + b db'_g),
+ * dbeta = sigmoid(100 beta) sum_g n_b,g db'_g (dgamma / dbeta nullable), sums in group order, no atomics.  Same domain. */
+typedef struct MftFwtGradJob {
+    const float* w; const float* b; const float* gamma; const float* beta; const float* gm;
+    const float* dw_fold; const float* db_fold;
+    float* dw; float* db; float* dgamma; float* dbeta;
+    int C, col;
+} MftFwtGradJob;
+int mft_fwt_unfold(const MftFwtGradJob* jobs, int n_layers, int groups, int ld, const float* noise, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,8 @@ SIGNATURES = {
     "mft_graph_aggregate_backward": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
     "mft_build_graph_nodes_backward": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "mft_gather_query_scores_backward": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "mft_fwt_draw_fold": [_P, _I, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _P, _P],
+    "mft_fwt_unfold": [_P, _I, _I, _I, _P, _P],
 }
 # test / A-B hooks (include/mft_hip_testing.h): form selection for tests/ and tools/, never called by the product path
 TESTING_SIGNATURES = {

@@ -2,6 +2,8 @@
 HIP functional layer.  Parameters are repacked into the kernels' layouts lazily (cache keyed on the
 tensors' autograd version counters) and gradients are handed back in the reference's layouts.
 """
+import contextlib
+
 import torch
 
 from . import functional as Fn
@@ -68,6 +70,59 @@ def _eval_weights(mod, W):
     return stats
 
 
+# ---------------------------------------------------------------------------------------------- feature-wise transformation
+
+def is_feature_wise(mod):
+    """A backbone.ResNet built from SimpleBlock2 (ResNet10_FW)."""
+    return bool(getattr(mod, "feature_wise", False))
+
+
+def _base_params(mod):
+    """The parameters ResNet10 has too, in its order (the feature-wise transformation's gamma / beta sit in between)."""
+    if not is_feature_wise(mod):
+        return list(mod.parameters())
+    return [p for n, p in mod.named_parameters() if not n.endswith((".gamma", ".beta"))]
+
+
+def fwt_seed(mod):
+    """The generator key of this process: the module's ``fwt_seed`` with the rank mixed in, so that ranks draw different noise and
+    the same (rank, seed, draw index) reproduces it."""
+    from . import parallel
+    return (int(mod.fwt_seed) + 0x9E3779B97F4A7C15 * parallel.world()[0]) & 0xFFFFFFFFFFFFFFFF
+
+
+def fwt_draw(mod, groups):
+    """Draw the noise of one train-mode forward of a ResNet10_FW module (``groups`` independent sets: one per lockstep episode, as
+    each episode is a forward call of its own in the reference) and fold it into the seven layers' affine parameters: ONE launch,
+    which also advances the module's draw index on the device."""
+    from . import backbone
+    named = dict(mod.named_parameters())
+    layers, need = [], []
+    for name, C, col in backbone.FWT_LAYERS:
+        w, b, gamma, beta = (named["%s.%s" % (name, k)] for k in ("weight", "bias", "gamma", "beta"))
+        for p in (w, b, gamma, beta):
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("ResNet10_FW: %s parameters must be contiguous float32 tensors on the GPU (no CPU fallback)" % name)
+        layers.append((name, C, col, w.detach(), b.detach(), gamma.detach().view(-1), beta.detach().view(-1)))
+        if gamma.requires_grad or beta.requires_grad:
+            need.append(name)
+    return FB.FwtState(layers, groups, backbone.FWT_COLS, fwt_seed(mod), mod.fwt_draw_index, noise_in=mod.__dict__.get("_fwt_forced"),
+                       need_gamma_beta=need)
+
+
+@contextlib.contextmanager
+def fwt_forced_noise(mod, noise):
+    """Tests and golden parity only: inside the block every train-mode forward of ``mod`` takes its normals from ``noise``
+    [groups, 2, 1856] (float32, on the module's device) instead of the generator; the draw index still advances."""
+    if not is_feature_wise(mod):
+        raise ValueError("fwt_forced_noise: not a ResNet10_FW module")
+    mod.__dict__["_fwt_forced"] = noise
+    try:
+        yield mod
+    finally:
+        mod.__dict__.pop("_fwt_forced", None)
+
+
 class _ResNet10Fn(torch.autograd.Function):
     """ResNet10 forward on HIP; backward through the last block only (the inner-loop regime: everything
     below trunk.7 is frozen -- finetune.py:242-252)."""
@@ -111,7 +166,8 @@ class _ResNet10FullFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x_nhwc, groups, *params):
         W = module_weights(mod)
-        feat, tape = FB.resnet10_forward_taped(W, x_nhwc, running=_running(mod), groups=groups)
+        fwt = fwt_draw(mod, groups) if is_feature_wise(mod) else None
+        feat, tape = FB.resnet10_forward_taped(W, x_nhwc, running=_running(mod), groups=groups, fwt=fwt)
         ctx.tape, ctx.W, ctx.mod = tape, W, mod
         return feat
 
@@ -121,7 +177,7 @@ class _ResNet10FullFn(torch.autograd.Function):
         names = [n for n, _ in mod.named_parameters()]
         need = [p.requires_grad for p in mod.parameters()]
         g = FB.resnet10_backward(ctx.W, ctx.tape, dfeat.contiguous().float(), set(names))
-        out = [g[nm] if r else None for nm, r in zip(names, need)]
+        out = [g[nm] if r else None for nm, r in zip(names, need)]         # (gamma / beta of a feature-wise layer: frozen by default)
         return (None, None, None) + tuple(out)
 
 
@@ -208,7 +264,7 @@ def resnet10_module_forward(mod, x, groups=1):
     """backbone.ResNet.forward: x NCHW [n,3,H,W] on the GPU -> [n,512].  ``groups`` > 1 (meta-training only): the n images are
     ``groups`` episodes one after the other, each a BatchNorm mini-batch of its own (GnnNet.set_forward_loss_lockstep)."""
     _require_cuda(x, "ResNet10.forward")
-    if groups != 1 and not (mod.training and torch.is_grad_enabled() and all(p.requires_grad for p in mod.parameters())):
+    if groups != 1 and not (mod.training and torch.is_grad_enabled() and all(p.requires_grad for p in _base_params(mod))):
         raise NotImplementedError("several BatchNorm groups per call exist on the meta-training path only (train mode, every "
                                   "backbone parameter trainable)")
     if x.dim() == 4 and x.dtype == torch.float32 and x.permute(0, 2, 3, 1).is_contiguous():
@@ -225,6 +281,16 @@ def resnet10_module_forward(mod, x, groups=1):
         W = module_weights(mod)
         n = xn.shape[0]
         return Fn.resnet10_forward(W, xn, arena_for(xn.device), ipg=n, fixed=_eval_weights(mod, W), tag="evl%d" % n).clone()
+    if is_feature_wise(mod):
+        # train-mode ResNet10_FW: always the taped launches (the only ones that take a per-group affine); without autograd the
+        # tape is dropped.  The noise stays on: the reference draws in every train-mode forward.
+        base = _base_params(mod)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            if not any(p.requires_grad for p in base[:-9]):
+                raise NotImplementedError("ResNet10_FW: the last-block-only backward (the inner-loop regime) is not built for the "
+                                          "feature-wise transformation backbone; train it with every parameter trainable")
+            return _ResNet10FullFn.apply(mod, xn, groups, *params)
+        return FB.resnet10_forward_taped(module_weights(mod), xn, running=_running(mod), groups=groups, fwt=fwt_draw(mod, groups))[0]
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         if any(p.requires_grad for p in params[:-9]):
             out = _ResNet10FullFn.apply(mod, xn, groups, *params)       # meta-training: gradients for the whole backbone

@@ -60,6 +60,62 @@ class SimpleBlock(nn.Module):
         raise RuntimeError("SimpleBlock is executed by ResNet.forward on the HIP path, not on its own")
 
 
+class FeatureWiseTransformation2d_fw(nn.BatchNorm2d):
+    """Feature-wise transformation layer of Tseng et al. (ICLR 2020; backbone.py:313-350): a BatchNorm2d whose train-mode output is
+    perturbed per channel, y = (1 + n_g softplus(gamma)) bn(x) + n_b softplus(beta), n_g, n_b ~ N(0, 1) drawn per call.  A parameter
+    container like the other children: ``gamma`` / ``beta`` [1, C, 1, 1] (0.3 / 0.5, frozen unless the user turns their
+    ``requires_grad`` on) sit behind ``weight`` / ``bias``; the arithmetic runs in csrc/fwt.hip through ResNet.forward."""
+    feature_augment = True
+
+    def __init__(self, num_features, momentum=0.1, track_running_stats=True):
+        super().__init__(num_features, momentum=momentum, track_running_stats=track_running_stats)
+        self.gamma = nn.Parameter(torch.ones(1, num_features, 1, 1) * 0.3)
+        self.beta = nn.Parameter(torch.ones(1, num_features, 1, 1) * 0.5)
+        self.gamma.requires_grad = False
+        self.beta.requires_grad = False
+
+    def forward(self, x):
+        raise RuntimeError("FeatureWiseTransformation2d_fw is executed by ResNet.forward on the HIP path, not on its own")
+
+
+class SimpleBlock2(SimpleBlock):
+    """SimpleBlock whose BN2 and BNshortcut are feature-wise transformation layers (backbone.py:90-130); BN1 stays plain.  Same
+    children in the same registration order, hence the reference's state-dict keys."""
+
+    def __init__(self, indim, outdim, half_res):
+        super().__init__(indim, outdim, half_res)
+        self.BN2 = FeatureWiseTransformation2d_fw(outdim)              # (assigning to a registered name keeps its position)
+        init_layer(self.BN2)
+        self.parametrized_layers[3] = self.BN2
+        if indim != outdim:
+            self.BNshortcut = FeatureWiseTransformation2d_fw(outdim)
+            init_layer(self.BNshortcut)
+            self.parametrized_layers[5] = self.BNshortcut
+
+
+# the noise layout of one ResNet10_FW forward (DESIGN.md section 15): [groups, 2, FWT_COLS], row 0 = n_g, row 1 = n_b, the seven
+# layers in the reference's draw order at these column offsets
+FWT_LAYERS = (("trunk.4.BN2", 64, 0), ("trunk.5.BN2", 128, 64), ("trunk.5.BNshortcut", 128, 192), ("trunk.6.BN2", 256, 320),
+              ("trunk.6.BNshortcut", 256, 576), ("trunk.7.BN2", 512, 832), ("trunk.7.BNshortcut", 512, 1344))
+FWT_COLS = 1856
+
+
+def plain_state_dict(sd):
+    """A ResNet10_FW (or method-on-ResNet10_FW) state dict without the feature-wise transformation parameters: what is left
+    loads into the same model built on ResNet10, where the transformation is the identity it is at test time."""
+    out = type(sd)()
+    for k, v in sd.items():
+        head, _, leaf = k.rpartition(".")
+        if leaf in ("gamma", "beta") and head.rpartition(".")[2] in ("BN2", "BNshortcut"):
+            continue
+        out[k] = v
+    return out
+
+
+def has_fwt_keys(sd):
+    return len(plain_state_dict(sd)) != len(sd)
+
+
 class ResNet(nn.Module):
     """ResNet container (backbone.py:401-439).  ``trunk`` keeps the reference's Sequential indices
     0 Conv2d, 1 BatchNorm2d, 2 ReLU, 3 MaxPool2d, 4-7 SimpleBlock, 8 AvgPool2d, 9 Flatten."""
@@ -91,6 +147,12 @@ class ResNet(nn.Module):
             self.final_feat_dim = [indim, 7, 7]
         self.flatten = flatten
         self.trunk = nn.Sequential(*trunk)
+        self.feature_wise = block is SimpleBlock2
+        if self.feature_wise:
+            # the generator's state (csrc/fwt.hip): a 64-bit seed (plain attribute) and the draw index, advanced on the device by
+            # every train-mode forward (a buffer, so that it moves with .cuda() and copies with deepcopy; not in the state dict)
+            self.fwt_seed = 0
+            self.register_buffer("fwt_draw_index", torch.zeros(1, dtype=torch.int64), persistent=False)
 
     def forward(self, x):
         if not self.flatten:
@@ -100,6 +162,11 @@ class ResNet(nn.Module):
 
 def ResNet10(flatten=True):
     return ResNet(SimpleBlock, [1, 1, 1, 1], [64, 128, 256, 512], flatten)
+
+
+def ResNet10_FW(flatten=True):
+    """ResNet10 with a feature-wise transformation layer at the end of every residual block (backbone.py:521-522)."""
+    return ResNet(SimpleBlock2, [1, 1, 1, 1], [64, 128, 256, 512], flatten)
 
 
 class _WeightNormLinear(nn.Module):

@@ -298,6 +298,7 @@ class FinetuneEngine:
         (ops.ridge_forward with its softmax epilogue, all E episodes per launch) on the final-pass features; ``head_state`` holds
         ``scale``."""
         assert mode in ("gnn", "linear", "proto", "dist", "matching", "ridge")
+        refuse_feature_wise(state, "FinetuneEngine")
         self.mode = mode
         self.views = mode not in ("linear", "dist")      # the inner loop trains on every view (finetune()); "linear" / "dist" on view 0 only
         # ``graph``: capture one inner step (single stream) as a hipGraph and replay it for every step -- ~40 launches
@@ -1062,6 +1063,17 @@ def _trunk_running_ema(st, arena_t, running, H):
                                               ops.BN_EPS, 0.1, ops._p(rm), ops._p(rv), ops._stream()), "mft_bn_running_ema")
 
 
+def refuse_feature_wise(what, who):
+    """The test-time kernels have no per-episode BatchNorm affine, so a ResNet10_FW backbone (a module, or a state dict with the
+    feature-wise transformation's ``gamma`` / ``beta`` keys) is refused.  At test time the transformation is switched off here
+    (DESIGN.md section 15): drop the keys with backbone.plain_state_dict and evaluate on ResNet10."""
+    from . import backbone
+    fw = getattr(what, "feature_wise", False) if isinstance(what, torch.nn.Module) else backbone.has_fwt_keys(what)
+    if fw:
+        raise NotImplementedError("%s: a ResNet10_FW backbone is not on the test-time HIP path (the fused kernels have no per-episode "
+                                  "affine); evaluate its weights on ResNet10 with backbone.plain_state_dict(state)" % who)
+
+
 def adapt_last_block(feature_mod, x_a, y_a, epochs, batch_size, lr=0.01, perms=None):
     """The inner loop of GnnNet.set_forward_finetune (gnnnet.py:126-177) for one episode: Adam(lr=0.01) on the last
     ResNet block of a *copy* of ``feature_mod`` over ``epochs`` permutations of the support set in mini-batches of
@@ -1069,6 +1081,7 @@ def adapt_last_block(feature_mod, x_a, y_a, epochs, batch_size, lr=0.01, perms=N
     Returns {state_dict key: tensor} for the nine adapted tensors and the BatchNorm running buffers (valid until the next call).
     From the second episode of a shape on, the whole loop is ONE hipGraph replay (MFT_ADAPT_GRAPH=0: eager launches)."""
     from . import autograd_ops as AG
+    refuse_feature_wise(feature_mod, "adapt_last_block")
     dev = x_a.device
     n, _, H, _ = x_a.shape
     W = AG.module_weights(feature_mod)                 # refreshed in place when the module's parameters moved on

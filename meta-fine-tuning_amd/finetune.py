@@ -189,13 +189,24 @@ def _take_ready(liz_x, kind, freeze_backbone=False, state_in=None, model=None):
 
 # ------------------------------------------------------------------------------------------------ per-episode entry points
 
+def refuse_feature_wise_model(model_name, who):
+    if model_name == 'ResNet10_FW':
+        raise NotImplementedError("%s --model ResNet10_FW: the feature-wise transformation backbone is a meta-training backbone; at "
+                                  "test time the transformation is off, so evaluate the checkpoint with --model ResNet10 after "
+                                  "backbone.plain_state_dict(state) dropped its gamma / beta keys" % who)
+
+
 def _params_of(p):
+    if p is not None:
+        refuse_feature_wise_model(p.model, "finetune")
     if p is None or p.model != 'ResNet10':
         raise RuntimeError("finetune.params must be set (Namespace(model='ResNet10', fine_tune_epoch=...))")
     return p
 
 
 def _eval_backbone(state_in, model_name):
+    refuse_feature_wise_model(model_name, "finetune")
+    eng.refuse_feature_wise(state_in, "finetune")
     feat = model_dict[model_name](flatten=True)
     feat.load_state_dict({k.replace("feature.", "", 1): v for k, v in _feature_items(state_in)})
     return feat.cuda().eval()
@@ -925,6 +936,7 @@ def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
     global params
     np.random.seed(10)                                               # finetune.py:425
     params = parse_args('train', argv)
+    refuse_feature_wise_model(params.model, "finetune.main")
     parallel.limit_host_threads()
     _init_distributed()
     rank, _W = parallel.world()

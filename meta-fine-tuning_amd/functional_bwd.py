@@ -6,6 +6,8 @@ Covers what ``loss.backward()`` differentiates in MetaTemplate.train_loop2 / tra
 One episode per call as the reference's loops run it -- or k episodes in lockstep (``groups`` / ``episodes``: every BatchNorm keeps
 per-episode statistics, the parameter gradients are the sums over the k episodes); gradients come back in the reference's layouts.
 """
+import ctypes
+
 import torch
 
 from . import functional as Fn
@@ -109,16 +111,107 @@ def colsum(x2d, C):
     return out
 
 
+# =========================================================================================== feature-wise transformation
+
+class _FwtJob(ctypes.Structure):
+    """MftFwtJob (include/mft_hip.h)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w", "b", "gamma", "beta", "w_fold", "b_fold", "gm")] + [("C", ctypes.c_int), ("col", ctypes.c_int)]
+
+
+class _FwtGradJob(ctypes.Structure):
+    """MftFwtGradJob (include/mft_hip.h)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w", "b", "gamma", "beta", "gm", "dw_fold", "db_fold", "dw", "db", "dgamma", "dbeta")] + \
+               [("C", ctypes.c_int), ("col", ctypes.c_int)]
+
+
+class FwtState:
+    """One forward's feature-wise transformation: ``layers`` = [(name, C, col, w, b, gamma, beta)] with the
+    four parameters as [C] fp32 device tensors.  ``draw`` issues the one draw-and-fold launch for all layers and ``groups`` noise sets
+    and leaves ``affine[name]`` = (w', b') [groups, C] for the BatchNorm launches, ``gm`` and ``noise`` [groups, 2, ld] for the
+    backward; ``unfold`` issues the one launch that turns the per-group gradients of (w', b') into those of the parameters."""
+
+    def __init__(self, layers, groups, ld, seed, index, noise_in=None, need_gamma_beta=(), want_words=False):
+        if not 1 <= len(layers) <= 8:
+            raise ValueError("FwtState: 1 to 8 layers per launch")
+        self.layers, self.groups, self.ld = list(layers), int(groups), int(ld)
+        dev = index.device
+        if noise_in is not None and (tuple(noise_in.shape) != (self.groups, 2, self.ld) or noise_in.dtype != torch.float32
+                                     or not noise_in.is_contiguous() or noise_in.device != dev):
+            raise ValueError("forced noise must be a contiguous float32 [%d, 2, %d] tensor on %s" % (self.groups, self.ld, dev))
+        tot = sum(c for _, c, *_ in self.layers)
+        self.fold = _empty((3, self.groups * tot), dev)               # w', b', gm: per layer a contiguous [groups, C] block
+        self.noise = _empty((self.groups, 2, self.ld), dev)
+        self.words = torch.empty((self.groups, 2, self.ld), device=dev, dtype=torch.int32) if want_words else None
+        self.need_gamma_beta = set(need_gamma_beta)
+        self.affine, self._gm, self._off = {}, {}, {}
+        arr = (_FwtJob * len(self.layers))()
+        off = 0
+        for a, (name, C, col, w, b, gamma, beta) in zip(arr, self.layers):
+            n = self.groups * C
+            wf, bf, gm = (self.fold[i, off:off + n].view(self.groups, C) for i in range(3))
+            self.affine[name], self._gm[name], self._off[name] = (wf, bf), gm, off
+            a.w, a.b, a.gamma, a.beta = (t.data_ptr() for t in (w, b, gamma, beta))
+            a.w_fold, a.b_fold, a.gm, a.C, a.col = wf.data_ptr(), bf.data_ptr(), gm.data_ptr(), C, col
+            off += n
+        self.tot = tot
+        L.check(L.lib().mft_fwt_draw_fold(arr, len(self.layers), self.groups, self.ld, int(seed) & 0xFFFFFFFFFFFFFFFF, ops._p(index),
+                                          ops._p(noise_in), ops._p(self.noise), ops._p(self.words), ops._stream()), "mft_fwt_draw_fold")
+        self.dfold = None
+
+    def grad_slots(self, name):
+        """(dw', db') [groups, C] of layer ``name``: where its BatchNorm backward writes the per-group gradients."""
+        if self.dfold is None:
+            self.dfold = _empty((2, self.groups * self.tot), self.fold.device)
+        C = self.affine[name][0].shape[1]
+        off = self._off[name]
+        return tuple(self.dfold[i, off:off + self.groups * C].view(self.groups, C) for i in range(2))
+
+    def unfold(self, grads):
+        """Writes '<name>.weight' / '.bias' (and '.gamma' / '.beta' [1, C, 1, 1] for the layers in ``need_gamma_beta``) into ``grads``."""
+        dev = self.fold.device
+        arr = (_FwtGradJob * len(self.layers))()
+        for a, (name, C, col, w, b, gamma, beta) in zip(arr, self.layers):
+            dwf, dbf = self.grad_slots(name)
+            dw, db = _empty((C,), dev), _empty((C,), dev)
+            a.w, a.b, a.gamma, a.beta, a.gm = (t.data_ptr() for t in (w, b, gamma, beta, self._gm[name]))
+            a.dw_fold, a.db_fold, a.dw, a.db, a.C, a.col = dwf.data_ptr(), dbf.data_ptr(), dw.data_ptr(), db.data_ptr(), C, col
+            grads[name + ".weight"], grads[name + ".bias"] = dw, db
+            if name in self.need_gamma_beta:
+                dg, dbt = _empty((1, C, 1, 1), dev), _empty((1, C, 1, 1), dev)
+                a.dgamma, a.dbeta = dg.data_ptr(), dbt.data_ptr()
+                grads[name + ".gamma"], grads[name + ".beta"] = dg, dbt
+        L.check(L.lib().mft_fwt_unfold(arr, len(self.layers), self.groups, self.ld, ops._p(self.noise), ops._stream()), "mft_fwt_unfold")
+
+
+def bn_bwd_per_group(x2d, dy2d, C, rows, mean, rstd, gamma_g, dg_g, db_g, y_act=None, act=NONE, groups=1):
+    """BatchNorm backward with a per-group affine ``gamma_g`` [groups, C] (a feature-wise transformation layer's folded weight):
+    -> dx; the per-group parameter gradients go to ``dg_g`` / ``db_g`` [groups, C]."""
+    dev = x2d.device
+    dx = _empty(x2d.shape, dev)
+    rpg = rows // groups
+    ws = _empty((int(L.lib().mft_bn_backward_ws_floats(C, rpg, groups)),), dev)
+    rc = L.lib().mft_bn_backward_act(ops._p(x2d), x2d.shape[-1], ops._p(dy2d), dy2d.shape[-1], ops._p(y_act),
+                                     0 if y_act is None else y_act.shape[-1], ops._p(dx), dx.shape[-1], C, rpg, groups, ops._p(mean),
+                                     ops._p(rstd), ops._p(gamma_g), C, ops._p(dg_g), ops._p(db_g), act, ops.LRELU_SLOPE, ops._p(ws),
+                                     None, None, None, ops._stream())
+    L.check(rc, "mft_bn_backward_act")
+    return dx
+
+
 # =========================================================================================== ResNet10
 
-def resnet10_forward_taped(W, x, running=None, groups=1):
+def resnet10_forward_taped(W, x, running=None, groups=1, fwt=None):
     """x [n,H,W,3] NHWC, ``groups`` BatchNorm mini-batches of n / groups consecutive images (1 = the reference's loop: one episode per
     call; k = k episodes in lockstep, each with its own statistics, as k ranks of an episode-parallel run would have).
+    ``fwt`` (a drawn FwtState, ResNet10_FW in train mode): BN2 / BNshortcut of every block take its per-group affine (w', b');
+    None: exactly the launches of ResNet10.
     Returns (features [n,512], tape)."""
     n = x.shape[0]
     assert n % groups == 0
     dev = x.device
-    t = {"x": x, "n": n, "groups": groups}
+    t = {"x": x, "n": n, "groups": groups, "fwt": fwt}
+    if fwt is not None:
+        assert fwt.groups == groups
 
     def run(name):
         return None if running is None else running.get(name)
@@ -162,7 +255,11 @@ def resnet10_forward_taped(W, x, running=None, groups=1):
             r1 = ops.bn_apply(c1.view(-1, cout), cout, rows // groups, groups, m1, s1, g1, be1, act=RELU).view(n, OH, OH, cout)
         c2 = conv3x3(p + ".C2", r1, cout, cout, 1, rows)
         g2, be2 = W.bn[p + ".BN2"]
-        if cin != cout and small:
+        gbs = 0
+        if fwt is not None:            # per-group folded affine; the one-launch small form has no group stride for it: statistics + apply
+            g2, be2 = fwt.affine[p + ".BN2"]
+            gbs = cout
+        if cin != cout and small and fwt is None:
             # BN2 + BNshortcut + add + ReLU of a small block exit: ONE launch (both statistics taken in its first pass)
             sc = ops.conv2d(a, W.conv[p + ".shortcut"], cout, 1, 1, stride, 0)
             gs, bs = W.bn[p + ".BNshortcut"]
@@ -180,9 +277,9 @@ def resnet10_forward_taped(W, x, running=None, groups=1):
             sc = ops.conv2d(a, W.conv[p + ".shortcut"], cout, 1, 1, stride, 0)
             (m2, s2), (ms, ss) = ops.bn_stats_multi([(c2.view(-1, cout), cout, rows // groups, groups) + (run(p + ".BN2") or (None, None, None)),
                                                      (sc.view(-1, cout), cout, rows // groups, groups) + (run(p + ".BNshortcut") or (None, None, None))])
-            gs, bs = W.bn[p + ".BNshortcut"]
+            gs, bs = W.bn[p + ".BNshortcut"] if fwt is None else fwt.affine[p + ".BNshortcut"]
             out = ops.bn_apply(c2.view(-1, cout), cout, rows // groups, groups, m2, s2, g2, be2, act=RELU, res=sc.view(-1, cout),
-                               res_bn=(ms, ss, gs, bs)).view(n, OH, OH, cout)
+                               res_bn=(ms, ss, gs, bs), gb_group_stride=gbs).view(n, OH, OH, cout)
             b.update(sc=sc, ms=ms, ss=ss)
             b.update(c1=c1, m1=m1, s1=s1, r1=r1, c2=c2, m2=m2, s2=s2, out=out)
             blocks.append(b)
@@ -192,13 +289,13 @@ def resnet10_forward_taped(W, x, running=None, groups=1):
         if cin != cout:
             sc = ops.conv2d(a, W.conv[p + ".shortcut"], cout, 1, 1, stride, 0)
             ms, ss = bn_stats(sc.view(-1, cout), cout, rows, run(p + ".BNshortcut"), groups)
-            gs, bs = W.bn[p + ".BNshortcut"]
+            gs, bs = W.bn[p + ".BNshortcut"] if fwt is None else fwt.affine[p + ".BNshortcut"]
             out = ops.bn_apply(c2.view(-1, cout), cout, rows // groups, groups, m2, s2, g2, be2, act=RELU, res=sc.view(-1, cout),
-                               res_bn=(ms, ss, gs, bs)).view(n, OH, OH, cout)
+                               res_bn=(ms, ss, gs, bs), gb_group_stride=gbs).view(n, OH, OH, cout)
             b.update(sc=sc, ms=ms, ss=ss)
         else:
             out = ops.bn_apply(c2.view(-1, cout), cout, rows // groups, groups, m2, s2, g2, be2, act=RELU,
-                               res=a.view(-1, cin)).view(n, OH, OH, cout)
+                               res=a.view(-1, cin), gb_group_stride=gbs).view(n, OH, OH, cout)
         b.update(c1=c1, m1=m1, s1=s1, r1=r1, c2=c2, m2=m2, s2=s2, out=out)
         blocks.append(b)
         a = out
@@ -212,6 +309,7 @@ def resnet10_backward(W, t, dfeat, need, act_grads=None):
     ``act_grads`` (a dict, tests only): receives every block's activation gradients as 'trunk.N.out' (incoming, w.r.t. the block's
     output) and 'trunk.N.in' (outgoing, w.r.t. its input) -- references to the pass's own tensors, no copy and no launch."""
     n, groups = t["n"], t.get("groups", 1)
+    fwt = t.get("fwt")
     dev = dfeat.device
     grads = {}
     wb = ops.WgradBatch(WGRAD_BATCH)            # every layer's weight gradient is registered as the pass goes and run at its end
@@ -235,7 +333,15 @@ def resnet10_backward(W, t, dfeat, need, act_grads=None):
         d2 = d_out.view(-1, cout)
         g2 = W.bn[p + ".BN2"][0]
         dsc = None
-        if cin != cout and WGRAD_BATCH:
+        if fwt is not None:
+            # feature-wise transformation layers: the data gradient takes the group's folded weight, the per-group parameter
+            # gradients wait in the FwtState for the unfold launch at the end of the pass (the _multi job has no group stride)
+            dc2 = bn_bwd_per_group(b["c2"].view(-1, cout), d2, cout, rows, b["m2"], b["s2"], fwt.affine[p + ".BN2"][0],
+                                   *fwt.grad_slots(p + ".BN2"), y_act=o2, act=RELU, groups=groups)
+            if cin != cout:
+                dsc = bn_bwd_per_group(b["sc"].view(-1, cout), d2, cout, rows, b["ms"], b["ss"], fwt.affine[p + ".BNshortcut"][0],
+                                       *fwt.grad_slots(p + ".BNshortcut"), y_act=o2, act=RELU, groups=groups)
+        elif cin != cout and WGRAD_BATCH:
             # the backward of BN2 and of BNshortcut read the same d2 / o2: ONE launch triple for both (mft_bn_backward_act_multi)
             gs = W.bn[p + ".BNshortcut"][0]
             (dc2, dg, db), (dsc, dgs, dbs) = ops.bn_backward_multi([
@@ -244,7 +350,8 @@ def resnet10_backward(W, t, dfeat, need, act_grads=None):
             grads[p + ".BNshortcut.weight"], grads[p + ".BNshortcut.bias"] = dgs, dbs
         else:
             dc2, dg, db = bn_bwd(b["c2"].view(-1, cout), d2, cout, rows, b["m2"], b["s2"], g2, y_act=o2, act=RELU, groups=groups)
-        grads[p + ".BN2.weight"], grads[p + ".BN2.bias"] = dg, db
+        if fwt is None:
+            grads[p + ".BN2.weight"], grads[p + ".BN2.bias"] = dg, db
         dc2 = dc2.view(out.shape)
         grads[p + ".C2.weight"] = wb.add(b["r1"], dc2, cout, 3, 3, 1, 1)
         dr1 = dgrad3x3(p + ".C2", dc2, cout, cout, 1, rows, out.shape[1])
@@ -280,6 +387,8 @@ def resnet10_backward(W, t, dfeat, need, act_grads=None):
     grads["trunk.1.weight"], grads["trunk.1.bias"] = dg, db
     grads["trunk.0.weight"] = wb.add(t["x"], dc0.view(c0.shape), 64, 7, 7, 2, 3)
     wb.flush()
+    if fwt is not None:
+        fwt.unfold(grads)
     return grads
 
 

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import backbone
 
-model_dict = dict(ResNet10=backbone.ResNet10)      # ResNet10_FW / ResNet18 are off the hot path
+model_dict = dict(ResNet10=backbone.ResNet10, ResNet10_FW=backbone.ResNet10_FW)      # ResNet18 is off the hot path; ResNet10_FW: DESIGN §15
 
 # (flag, kwargs) for every script
 _COMMON = [

@@ -65,6 +65,20 @@ def resnet10_state_dict(seed=0, perturb_bn=True, prefix=""):
     return sd
 
 
+def resnet10_fw_state_dict(seed=0, perturb_bn=True, prefix=""):
+    """State dict of backbone.ResNet10_FW(flatten=True) in reference key order: ``resnet10_state_dict`` plus ``gamma`` (0.3) and
+    ``beta`` (0.5) [1, C, 1, 1] behind the ``bias`` of every BN2 / BNshortcut of the four blocks (backbone.py:313-326)."""
+    sd = OrderedDict()
+    for k, v in resnet10_state_dict(seed, perturb_bn, prefix).items():
+        sd[k] = v
+        head, _, leaf = k.rpartition(".")
+        if leaf == "bias" and head.rpartition(".")[2] in ("BN2", "BNshortcut"):
+            c = v.shape[0]
+            sd[head + ".gamma"] = torch.ones(1, c, 1, 1) * 0.3
+            sd[head + ".beta"] = torch.ones(1, c, 1, 1) * 0.5
+    return sd
+
+
 def gnn_head_state_dict(seed=1, n_way=5, perturb_bn=True):
     """fc.* and gnn.* entries of GnnNet (methods/gnnnet.py:30-31, methods/gnn.py:134-152)."""
     rs = np.random.RandomState(seed)

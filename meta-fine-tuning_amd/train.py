@@ -233,6 +233,9 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
         raise NotImplementedError("--method matchingnet --fine_tune: MatchingNet's first-order-MAML meta-training is not on the HIP path")
     if params.method == 'metaoptnet' and params.fine_tune:
         raise NotImplementedError("--method metaoptnet --fine_tune: MetaOptNet's first-order-MAML meta-training is not on the HIP path")
+    if params.model == 'ResNet10_FW' and params.fine_tune:
+        raise NotImplementedError("--model ResNet10_FW --fine_tune: the reference keeps the feature-wise noise on inside the inner loop, "
+                                  "and the fused inner-loop kernels have no per-episode affine; meta-train ResNet10_FW without --fine_tune")
     params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model, params.method)
     if params.train_aug:
         params.checkpoint_dir += '_aug'
