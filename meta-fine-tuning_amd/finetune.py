@@ -28,10 +28,12 @@ from . import parallel
 from . import settings
 from . import synthetic
 from .io_utils import model_dict, parse_args  # noqa: F401  (re-exported like the reference)
+from .methods.meta_template import HeadMethod
 
 params = None          # set by main(); finetune() reads params.model / params.fine_tune_epoch (finetune.py:185,261)
 
 LINEAR_EPOCHS = 20     # finetune.py:134 (total_epoch = 20 in finetune_linear)
+EPISODIC_METHODS = ("gnnnet", "protonet", "matchingnet", "metaoptnet")     # scored by finetune(): "gnnnet" + train.HEAD_METHODS
 
 
 # ------------------------------------------------------------------------------------------------ engine cache
@@ -99,39 +101,17 @@ def _head_key(model):
 
 
 def _engine_for(state_in, model, n_way, n_support, n_query, size, n_views, epochs, E, fold50=False):
-    """The finetune() engine for ``model``: a ProtoNet scores with its prototype head (mode "proto": no head weights, the key
-    says so), a MatchingNet with its LSTM / attention head (mode "matching", keyed on the head parameters), a
-    MetaOptNet with its ridge-regression head (mode "ridge", keyed on the scale parameter), anything else with the GNN head of its
-    fc / gnn modules."""
-    from .methods.protonet import ProtoNet
-    if isinstance(model, ProtoNet):
-        cfg = ("proto", n_way, n_support, n_query, size, n_views, epochs, E)
+    """The finetune() engine for ``model``: a HeadMethod (ProtoNet, MatchingNet, MetaOptNet) scores with its own head -- the
+    engine mode it names, keyed on that mode and the (address, version) of each parameter it lists (a ProtoNet lists none) --,
+    anything else with the GNN head of its fc / gnn modules."""
+    if isinstance(model, HeadMethod):
+        mode = model.ENGINE_MODE
+        cfg = (mode, *((p.data_ptr(), p._version) for p in model.head_params()), n_way, n_support, n_query, size, n_views, epochs, E)
 
-        def build_proto():
+        def build_head():
             return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
-                                      episodes_per_batch=E, mode="proto")
-        return _ENGINES.get(state_in, cfg, build_proto)
-    from .methods.matchingnet import MatchingNet
-    if isinstance(model, MatchingNet):
-        from . import autograd_ops as AG
-        from . import ops
-        plist = AG.matchingnet_params(model)
-        cfg = ("matching", tuple((p.data_ptr(), p._version) for p in plist), n_way, n_support, n_query, size, n_views, epochs, E)
-
-        def build_matching():
-            head = {k: p.detach() for k, p in zip(ops.MN_KEYS, plist)}
-            return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
-                                      episodes_per_batch=E, mode="matching", head_state=head)
-        return _ENGINES.get(state_in, cfg, build_matching)
-    from .methods.metaoptnet import MetaOptNet
-    if isinstance(model, MetaOptNet):
-        scale = model.scale
-        cfg = ("ridge", (scale.data_ptr(), scale._version), n_way, n_support, n_query, size, n_views, epochs, E)
-
-        def build_ridge():
-            return eng.FinetuneEngine(state_in, n_way, n_support, n_query, size, n_views=n_views, fine_tune_epoch=epochs,
-                                      episodes_per_batch=E, mode="ridge", head_state={"scale": scale.detach()})
-        return _ENGINES.get(state_in, cfg, build_ridge)
+                                      episodes_per_batch=E, mode=mode, head_state=model.head_state())
+        return _ENGINES.get(state_in, cfg, build_head)
     cfg = ("gnn", _head_key(model), n_way, n_support, n_query, size, n_views, epochs, E, fold50)
 
     def build():
@@ -336,7 +316,7 @@ def draw_episode_perms(method, n_way, n_support, n_views, fine_tune_epoch, rng=n
     lin = gnn = None
     if method in ("all", "baseline", "baseline++"):          # (finetune_dist is finetune_linear's loop: the same 20 draws)
         lin = [rng.permutation(n_way * n_support) for _ in range(LINEAR_EPOCHS)]
-    if method in ("all", "gnnnet", "protonet", "matchingnet", "metaoptnet"):
+    if method in ("all",) + EPISODIC_METHODS:
         gnn = [rng.permutation(n_way * n_support * (n_views + 1)) for _ in range(fine_tune_epoch)]
     return lin, gnn
 
@@ -485,7 +465,7 @@ def scores_batched(method, episodes, model, state_gnn, state_b, fine_tune_epoch,
         s_lin = finetune_linear_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, classifiers=classifiers)
     if method == "baseline++":
         s_lin = finetune_dist_batched(episodes, state_b, n_way, n_support, episodes_per_batch, perms=lin_p, heads=classifiers)
-    if method in ("all", "gnnnet", "protonet", "matchingnet", "metaoptnet"):
+    if method in ("all",) + EPISODIC_METHODS:
         s_gnn = finetune_batched(episodes, model, state_gnn, fine_tune_epoch, n_way, n_support, episodes_per_batch, perms=gnn_p)
     if parts:
         return s_lin, s_gnn
@@ -664,7 +644,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             return
         ids = batches[bi]
         if sampler is not None:
-            pipe = (method in ("gnnnet", "protonet", "matchingnet", "metaoptnet") and not freeze_backbone and model is not None)
+            pipe = (method in EPISODIC_METHODS and not freeze_backbone and model is not None)
             eps = []
             for i in ids:
                 src, P, _ = sampler.episode(seed0 + i, size, gen_examples)
@@ -699,7 +679,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
             ev.record()
         gens[bi] = (eps, ev, bad)
 
-    pipelined = (method in ("gnnnet", "protonet", "matchingnet", "metaoptnet") and not freeze_backbone and model is not None)
+    pipelined = (method in EPISODIC_METHODS and not freeze_backbone and model is not None)
     n_views = 2 + gen_examples
     engine = None
     flags, score_chunks = [], []

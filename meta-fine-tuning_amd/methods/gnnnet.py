@@ -84,18 +84,11 @@ class GnnNet(MetaTemplate):
         return scores.view(self.n_query, self.n_way, ns + 1, self.n_way)[:, :, -1].permute(1, 0, 2).contiguous().view(-1, self.n_way)
 
     def _y_query(self):
-        """np.repeat(range(n_way), n_query) on the device (gnnnet.py:220), uploaded once per (n_way, n_query): the per-step upload
-        is a synchronous copy, which a hipGraph capture of the step refuses."""
-        key = (self.n_way, self.n_query, torch.cuda.current_device())
-        y = self._yq_cache.get(key) if hasattr(self, "_yq_cache") else None
-        if y is None:
-            if not hasattr(self, "_yq_cache"):
-                self._yq_cache = {}
-            y = self._yq_cache[key] = torch.from_numpy(np.repeat(range(self.n_way), self.n_query)).cuda()
-        return y
+        """np.repeat(range(n_way), n_query) on the device (gnnnet.py:220)."""
+        return self._labels(1)
 
     def set_forward_loss(self, x):
-        y_query = self._y_query()
+        y_query = self._labels(1)
         scores = self.set_forward(x)
         return self.loss_fn(scores, y_query)
 
@@ -113,17 +106,10 @@ class GnnNet(MetaTemplate):
         """mean over the k episodes of ``set_forward_loss`` (gnnnet.py:219-224): its backward leaves the AVERAGE of the k episodes'
         gradients taken at the same parameters -- the step a k-rank episode-parallel run takes after its all-reduce
         (parallel.FlatGradBucket), here on one GPU with k times the work per launch."""
-        k = xs.size(0)
-        key = ("lockstep", self.n_way, self.n_query, k, torch.cuda.current_device())
-        if not hasattr(self, "_yq_cache"):
-            self._yq_cache = {}
-        y = self._yq_cache.get(key)
-        if y is None:
-            y = self._yq_cache[key] = torch.from_numpy(np.tile(np.repeat(range(self.n_way), self.n_query), k)).cuda()
-        return self.loss_fn(self.set_forward_lockstep(xs), y)
+        return self.loss_fn(self.set_forward_lockstep(xs), self._labels(xs.size(0)))
 
     def set_forward_loss_finetune(self, x):
-        y_query = self._y_query()
+        y_query = self._labels(1)
         scores = self.set_forward_finetune(x)
         return self.loss_fn(scores, y_query)
 
@@ -153,7 +139,7 @@ class GnnNet(MetaTemplate):
     def set_forward_loss_finetune_prepared(self, x):
         """The differentiable half of set_forward_loss_finetune, after ``_finetune_prepare(x)``: what the episode loop replays from
         a hipGraph (graph_step.for_loop)."""
-        return self.loss_fn(self._finetune_scores(x.cuda()), self._y_query())
+        return self.loss_fn(self._finetune_scores(x.cuda()), self._labels(1))
 
     def _finetune_prepare(self, x):
         """gnnnet.py:106-187: MAML_update, the inner loop on the support set, theta_pre / theta_adapted, the backbone takes the

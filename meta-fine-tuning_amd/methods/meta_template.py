@@ -10,6 +10,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import autograd_ops as AG
 from .. import graph_step, ops
 
 
@@ -46,6 +47,17 @@ class MetaTemplate(nn.Module):
             x = x.contiguous().view(self.n_way * (self.n_support + self.n_query), *x.size()[2:])
             z_all = self.feature.forward(x).view(self.n_way, self.n_support + self.n_query, -1)
         return z_all[:, :self.n_support], z_all[:, self.n_support:]
+
+    def _labels(self, k=1):
+        """np.tile(np.repeat(range(n_way), n_query), k) on the device, uploaded once per shape: a per-step upload is a
+        synchronous copy, which a hipGraph capture of the step refuses.  (Kept in ``__dict__``: not a module attribute, not in
+        the state dict.)"""
+        key = (self.n_way, self.n_query, k, torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_yq_cache", {})
+        y = cache.get(key)
+        if y is None:
+            y = cache[key] = torch.from_numpy(np.tile(np.repeat(range(self.n_way), self.n_query), k)).cuda()
+        return y
 
     def correct(self, x):
         scores = self.set_forward(x)
@@ -134,6 +146,78 @@ class MetaTemplate(nn.Module):
         linear_clf = nn.Linear(self.feat_dim, self.n_way).cuda()       # same torch-RNG draw as the reference
         return linear_head_adapt(z_support, y_support, z_query, linear_clf.weight.data, linear_clf.bias.data,
                                  self.n_way, self.n_support)
+
+
+class HeadMethod(MetaTemplate):
+    """A method that scores the backbone's features with ONE head call: ProtoNet, MatchingNet, MetaOptNet.  A subclass supplies
+    its constructor, ``_head`` and -- where its launchers have a bounded domain -- ``_check``; for test-time fine-tuning
+    (finetune._engine_for) it names its FinetuneEngine mode and the head weights that engine scores with.  The reference's
+    first-order-MAML ``--fine_tune`` path (set_forward_finetune / MAML_update) is not on the HIP path and raises."""
+    METHOD = None           # the --method name of train.py
+    ENGINE_MODE = None      # the FinetuneEngine mode that scores with this head
+
+    def _head(self, feats, n_query, episodes=1):
+        """feats [episodes * n_way * (n_support + n_query), D] -> scores [episodes * n_way * n_query, n_way]."""
+        raise NotImplementedError
+
+    def _check(self, n_query):
+        """Raise for an episode shape outside the head's domain (set_forward calls it before the backbone forward: a refused shape
+        does not first cost a trunk pass)."""
+
+    def head_params(self):
+        """The parameters that identify the head in the engine cache's key."""
+        return []
+
+    def head_state(self):
+        """``head_state`` of the FinetuneEngine (None: the head has no weights)."""
+        return None
+
+    # ------------------------------------------------------------------ forward
+    def set_forward(self, x, is_feature=False):
+        """x [n_way, n_support+n_query, 3,H,W] (or features [n_way, n_support+n_query, D]) -> scores [n_way*n_query, n_way],
+        row = class*n_query + q.  With ``freeze_backbone`` the backbone parameters stop requiring gradients (parse_feature)."""
+        x = x.cuda()
+        n_query = x.size(1) - self.n_support
+        self._check(n_query)
+        if is_feature:
+            feats = x.reshape(-1, x.size(-1))
+        else:
+            if self.freeze_backbone:
+                for p in self.feature.parameters():
+                    p.requires_grad = False
+            feats = self.feature(x.reshape(-1, *x.size()[2:]))
+        return self._head(feats, n_query)
+
+    def set_forward_loss(self, x):
+        return self.loss_fn(self.set_forward(x), self._labels(1))
+
+    # ------------------------------------------------------------------ k episodes in lockstep (opt-in, train.py --episodes_per_rank k)
+    def set_forward_lockstep(self, xs):
+        """xs [k, n_way, n_support+n_query, 3,H,W]: k episodes through one sequence of launches (per-episode BatchNorm statistics
+        in the backbone, every head launch for all k).  Scores [k*n_way*n_query, n_way], episode after episode."""
+        xs = xs.cuda()
+        k = xs.size(0)
+        feats = AG.resnet10_module_forward(self.feature, xs.reshape(-1, *xs.size()[3:]), groups=k)
+        return self._head(feats, xs.size(2) - self.n_support, episodes=k)
+
+    def set_forward_loss_lockstep(self, xs):
+        """Mean over the k episodes of ``set_forward_loss``: its backward leaves the average of the k episodes' gradients."""
+        return self.loss_fn(self.set_forward_lockstep(xs), self._labels(xs.size(0)))
+
+    # ------------------------------------------------------------------ first-order MAML (not on the HIP path)
+    def _refuse_fine_tune(self, what):
+        raise NotImplementedError("%s.%s: the --fine_tune (first-order MAML) meta-training of %s is not on the HIP path; "
+                                  "meta-train with train.py --method %s without --fine_tune"
+                                  % (type(self).__name__, what, self.METHOD, self.METHOD))
+
+    def MAML_update(self):
+        self._refuse_fine_tune("MAML_update")
+
+    def set_forward_finetune(self, x):
+        self._refuse_fine_tune("set_forward_finetune")
+
+    def set_forward_loss_finetune(self, x):
+        return self.set_forward_finetune(x)
 
 
 class LockstepLoader:

@@ -15,6 +15,8 @@ from .methods.matchingnet import MatchingNet
 from .methods.metaoptnet import MetaOptNet
 from .methods.protonet import ProtoNet
 
+HEAD_METHODS = {'protonet': ProtoNet, 'matchingnet': MatchingNet, 'metaoptnet': MetaOptNet}      # --method -> class (train.py:138-139)
+
 
 class SyntheticEpisodeLoader:
     """Stand-in for miniImageNet_few_shot.SetDataManager(...).get_data_loader(): ``n_episode`` episodes of
@@ -188,11 +190,11 @@ def train(base_loader, model, optimization, start_epoch, stop_epoch, params, var
         if params.method in ('baseline', 'baseline++'):
             model.train_loop(epoch, base_loader, optimizer)              # train.py:41-42: every other method -> train_loop
         elif not params.fine_tune and getattr(params, "episodes_per_rank", 1) > 1:
-            if fifty and params.method not in ('protonet', 'matchingnet', 'metaoptnet'):
+            if fifty and params.method not in HEAD_METHODS:
                 raise NotImplementedError("--episodes_per_rank with the 50-shot loops")
             model.train_loop_lockstep(epoch, base_loader, optimizer, params.episodes_per_rank)
         elif not params.fine_tune:
-            if params.method in ('protonet', 'matchingnet', 'metaoptnet'):
+            if params.method in HEAD_METHODS:
                 model.train_loop(epoch, base_loader, optimizer)          # train.py:48-49 / train_50.py:48-49: the else branch
             else:
                 (model.train_loop50 if fifty else model.train_loop2)(epoch, base_loader, optimizer)
@@ -227,12 +229,9 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet'):
         raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'baseline' and 'baseline++' are on the HIP path"
                                   % params.method)
-    if params.method == 'protonet' and params.fine_tune:
-        raise NotImplementedError("--method protonet --fine_tune: ProtoNet's first-order-MAML meta-training is not on the HIP path")
-    if params.method == 'matchingnet' and params.fine_tune:
-        raise NotImplementedError("--method matchingnet --fine_tune: MatchingNet's first-order-MAML meta-training is not on the HIP path")
-    if params.method == 'metaoptnet' and params.fine_tune:
-        raise NotImplementedError("--method metaoptnet --fine_tune: MetaOptNet's first-order-MAML meta-training is not on the HIP path")
+    if params.method in HEAD_METHODS and params.fine_tune:
+        raise NotImplementedError("--method %s --fine_tune: %s's first-order-MAML meta-training is not on the HIP path"
+                                  % (params.method, HEAD_METHODS[params.method].__name__))
     if params.model == 'ResNet10_FW' and params.fine_tune:
         raise NotImplementedError("--model ResNet10_FW --fine_tune: the reference keeps the feature-wise noise on inside the inner loop, "
                                   "and the fused inner-loop kernels have no per-episode affine; meta-train ResNet10_FW without --fine_tune")
@@ -254,12 +253,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
                                                 aug=params.train_aug, rank=rank, world=W)
         else:
             base_loader = SyntheticEpisodeLoader(params.train_n_way, params.n_shot, n_query, size, n_episode, rank=rank, world=W)
-        if params.method == 'protonet':
-            cls = ProtoNet                                               # train.py:138-139
-        elif params.method == 'matchingnet':
-            cls = MatchingNet
-        elif params.method == 'metaoptnet':
-            cls = MetaOptNet
+        if params.method in HEAD_METHODS:
+            cls = HEAD_METHODS[params.method]
         else:
             cls = gnnnet_copy.GnnNet if (variant50 and params.n_shot == 50) else GnnNet          # train_50.py:154-157
         torch.manual_seed(0) if W > 1 else None

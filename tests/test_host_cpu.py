@@ -678,3 +678,17 @@ def test_round6_late_knobs_and_form_predicates():
     assert "GEMM_RK_ROWS" in src and "ops.gemm_rk" in src and "ops.gemm(" in src          # both forms reachable, chosen by size
     assert ops.bn_forward_small_ok(48, 480) and ops.bn_forward_small_ok(128, 105)          # the head's BatchNorm1d layers
     assert not ops.bn_forward_small_ok(512, 945) and not ops.bn_forward_small_ok(6, 100)   # trunk.7 (measured slower), C % 4 != 0
+
+
+def test_head_method_table_and_episodic_methods_agree():
+    """train.HEAD_METHODS and finetune.EPISODIC_METHODS name the same head methods, every one of them refuses --fine_tune by its
+    own name, and no two share a FinetuneEngine mode."""
+    from meta_fine_tuning_amd import finetune, train
+    for name in train.HEAD_METHODS:
+        with pytest.raises(NotImplementedError, match="first-order-MAML") as e:
+            train.main(['--method', name, '--fine_tune', '--stop_epoch', '1'])
+        assert name in str(e.value)
+    assert finetune.EPISODIC_METHODS == ("gnnnet",) + tuple(train.HEAD_METHODS)
+    modes = [cls.ENGINE_MODE for cls in train.HEAD_METHODS.values()]
+    assert len(set(modes)) == len(modes) == 3 and all(modes)
+    assert [cls.METHOD for cls in train.HEAD_METHODS.values()] == list(train.HEAD_METHODS)

@@ -337,8 +337,8 @@ def test_graphed_episode_loop_is_bit_identical(capsys, monkeypatch):
 
 
 def test_metaoptnet_step_issues_no_aten_device_kernels():
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "metaoptnet_step_worker.py")
-    r = subprocess.run([sys.executable, worker], capture_output=True, text=True, timeout=900)
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "method_step_worker.py")
+    r = subprocess.run([sys.executable, worker, "metaoptnet"], capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
     assert lines, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     res = json.loads(lines[-1][len("RESULT "):])

@@ -8,16 +8,16 @@ The yardstick of the feature-wise transformation backbone is the plain ResNet10 
     python tools/fwt_step_time.py [steps] [--launches | --one ResNet10_FW]"""
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import meta_fine_tuning_amd  # noqa: E402,F401
-from meta_fine_tuning_amd import _lib, graph_step, optim, synthetic  # noqa: E402
+from meta_fine_tuning_amd import _lib, synthetic  # noqa: E402
 from meta_fine_tuning_amd.io_utils import model_dict  # noqa: E402
 from meta_fine_tuning_amd.methods.gnnnet import GnnNet  # noqa: E402
 from meta_fine_tuning_amd.methods.protonet import ProtoNet  # noqa: E402
+from graphed_step_timer import time_graphed_step  # noqa: E402
 
 one = sys.argv[sys.argv.index("--one") + 1] if "--one" in sys.argv else None
 args = [a for a in sys.argv[1:] if not a.startswith("--") and a != one]
@@ -36,30 +36,10 @@ def build(cls, name):
 
 
 def run(cls, name, k):
-    model = build(cls, name)
-    opt = optim.Adam(model.parameters())
-    eps = [synthetic.train_episode(5000 + i, 5, 5, 16, 84) for i in range(2 * k)]
-    xs = [torch.stack(eps[j * k:(j + 1) * k]).cuda() if k > 1 else eps[j].cuda() for j in range(2)]
-    loss_fn = model.set_forward_loss_lockstep if k > 1 else model.set_forward_loss
-    step = graph_step.for_loop(model, loss_fn)
-    assert step is not None, "graphed steps are disabled (MFT_TRAIN_GRAPH)"
-    for i in range(6):                                   # eager warm-up, capture, first replays
-        step(xs[i % 2], opt)
-        opt.step()
-    torch.cuda.synchronize()
-    assert step.graph is not None and not step.failed
-    best = None
-    for _ in range(3):                                   # three timed passes: the minimum and the spread
-        t0 = time.perf_counter()
-        for i in range(steps):
-            loss = step(xs[i % 2], opt)
-            opt.step()
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / steps
-        best = (dt, dt) if best is None else (min(best[0], dt), max(best[1], dt))
+    best, worst, loss = time_graphed_step(build(cls, name), k, steps, passes=3)      # three timed passes: the minimum and the spread
     print("%-8s %-11s k = %d  %7.3f ms per step (slowest of 3 passes %7.3f)  %7.1f episodes/s  loss %.5f"
-          % (cls.__name__, name, k, best[0] * 1e3, best[1] * 1e3, k / best[0], float(loss.detach())), flush=True)
-    return best[0]
+          % (cls.__name__, name, k, best * 1e3, worst * 1e3, k / best, loss), flush=True)
+    return best
 
 
 def launches():

@@ -14,10 +14,11 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import meta_fine_tuning_amd  # noqa: E402,F401
 from meta_fine_tuning_amd import autograd_ops as AG  # noqa: E402
-from meta_fine_tuning_amd import graph_step, optim, synthetic  # noqa: E402
+from meta_fine_tuning_amd import synthetic  # noqa: E402
 from meta_fine_tuning_amd.io_utils import model_dict  # noqa: E402
 from meta_fine_tuning_amd.methods.matchingnet import MatchingNet  # noqa: E402
 from meta_fine_tuning_amd.methods.protonet import ProtoNet  # noqa: E402
+from graphed_step_timer import time_graphed_step  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 
@@ -34,25 +35,8 @@ def make(cls):
 
 
 def run(cls, k):
-    model = make(cls)
-    opt = optim.Adam(model.parameters())
-    eps = [synthetic.train_episode(5000 + i, 5, 5, 16, 84) for i in range(2 * k)]
-    xs = [torch.stack(eps[j * k:(j + 1) * k]).cuda() if k > 1 else eps[j].cuda() for j in range(2)]
-    loss_fn = model.set_forward_loss_lockstep if k > 1 else model.set_forward_loss
-    step = graph_step.for_loop(model, loss_fn)
-    assert step is not None, "graphed steps are disabled (MFT_TRAIN_GRAPH)"
-    for i in range(6):                                   # eager warm-up, capture, first replays
-        step(xs[i % 2], opt)
-        opt.step()
-    torch.cuda.synchronize()
-    assert step.graph is not None and not step.failed
-    t0 = time.perf_counter()
-    for i in range(steps):
-        loss = step(xs[i % 2], opt)
-        opt.step()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    print("%-11s k = %d  %7.3f ms per step  %7.1f episodes/s  loss %.5f" % (cls.__name__, k, dt * 1e3, k / dt, float(loss.detach())), flush=True)
+    dt, _, loss = time_graphed_step(make(cls), k, steps)
+    print("%-11s k = %d  %7.3f ms per step  %7.1f episodes/s  loss %.5f" % (cls.__name__, k, dt * 1e3, k / dt, loss), flush=True)
     return dt * 1e3
 
 

@@ -6,17 +6,17 @@ MetaTemplate._episode_loop) of MetaOptNet next to ProtoNet (the same backbone, a
     python tools/metaoptnet_step_time.py [steps]"""
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import meta_fine_tuning_amd  # noqa: E402,F401
 from meta_fine_tuning_amd import autograd_ops as AG  # noqa: E402
-from meta_fine_tuning_amd import _lib, graph_step, ops, optim, synthetic  # noqa: E402
+from meta_fine_tuning_amd import _lib, ops, synthetic  # noqa: E402
 from meta_fine_tuning_amd.io_utils import model_dict  # noqa: E402
 from meta_fine_tuning_amd.methods.metaoptnet import MetaOptNet  # noqa: E402
 from meta_fine_tuning_amd.methods.protonet import ProtoNet  # noqa: E402
+from graphed_step_timer import time_graphed_step  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 
@@ -26,26 +26,8 @@ def run(cls, k):
     model = cls(model_dict["ResNet10"], n_way=5, n_support=5).cuda()
     sd = synthetic.gnnnet_state_dict(seed=0)
     model.load_state_dict({n: v for n, v in sd.items() if n in model.state_dict()}, strict=False)
-    model.train()
-    model.n_query = 16
-    opt = optim.Adam(model.parameters())
-    eps = [synthetic.train_episode(5000 + i, 5, 5, 16, 84) for i in range(2 * k)]
-    xs = [torch.stack(eps[j * k:(j + 1) * k]).cuda() if k > 1 else eps[j].cuda() for j in range(2)]
-    loss_fn = model.set_forward_loss_lockstep if k > 1 else model.set_forward_loss
-    step = graph_step.for_loop(model, loss_fn)
-    assert step is not None, "graphed steps are disabled (MFT_TRAIN_GRAPH)"
-    for i in range(6):                                   # eager warm-up, capture, first replays
-        step(xs[i % 2], opt)
-        opt.step()
-    torch.cuda.synchronize()
-    assert step.graph is not None and not step.failed
-    t0 = time.perf_counter()
-    for i in range(steps):
-        loss = step(xs[i % 2], opt)
-        opt.step()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    print("%-10s k = %d  %7.3f ms per step  %7.1f episodes/s  loss %.5f" % (cls.__name__, k, dt * 1e3, k / dt, float(loss.detach())), flush=True)
+    dt, _, loss = time_graphed_step(model, k, steps)
+    print("%-10s k = %d  %7.3f ms per step  %7.1f episodes/s  loss %.5f" % (cls.__name__, k, dt * 1e3, k / dt, loss), flush=True)
 
 
 def _time(fn, reps):
