@@ -165,7 +165,6 @@ struct ApplyArgs {
     const float* mean; const float* rstd; const float* gamma; const float* beta; long long gbs;
     const float* res; int ldr; const float* rmean; const float* rrstd; const float* rgamma; const float* rbeta;
     int act; float slope;
-    unsigned short* planes; long long plane_stride;      // optional bf16x3 planes of y ([3][rows][C], csrc/conv_x3.hip operand)
 };
 
 __device__ __forceinline__ float act_f(float v, int act, float slope) {
@@ -174,7 +173,6 @@ __device__ __forceinline__ float act_f(float v, int act, float slope) {
     return v;
 }
 
-template <bool PLANES>
 __device__ __forceinline__ void bn_apply_blocks(const ApplyArgs& p, const int block, const int n_blocks) {
     const int cq = p.C >> 2;
     const long long total = (long long)p.n_groups * p.rows_per_group * cq;
@@ -215,21 +213,12 @@ __device__ __forceinline__ void bn_apply_blocks(const ApplyArgs& p, const int bl
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = act_f(o[e], act, p.slope);
-        if (!PLANES || p.y) *(f32x4*)(p.y + row * p.ldy + c) = o;
-        if constexpr (PLANES) {
-            mft_u32x2 p1, p2, p3;
-            mft_split4_bf16(o, p1, p2, p3);
-            unsigned short* q = p.planes + row * p.C + c;
-            *(mft_u32x2*)(q) = p1;
-            *(mft_u32x2*)(q + p.plane_stride) = p2;
-            *(mft_u32x2*)(q + 2 * p.plane_stride) = p3;
-        }
+        *(f32x4*)(p.y + row * p.ldy + c) = o;
     }
 }
 
-template <bool PLANES>
 __global__ __launch_bounds__(256) void bn_apply_kernel(ApplyArgs p) {
-    bn_apply_blocks<PLANES>(p, blockIdx.x, gridDim.x);
+    bn_apply_blocks(p, blockIdx.x, gridDim.x);
 }
 
 // several apply problems in one launch (mft_bn_apply_multi): block b works for the job j with start[j] <= b < start[j + 1], as block
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(256) void bn_apply_multi_kernel(ApplyMultiArgs a) {
 #pragma unroll 1
     while (j + 1 < a.n && (int)blockIdx.x >= a.start[j + 1]) ++j;
     const ApplyArgs p = a.job[j];
-    bn_apply_blocks<false>(p, blockIdx.x - a.start[j], a.start[j + 1] - a.start[j]);
+    bn_apply_blocks(p, blockIdx.x - a.start[j], a.start[j + 1] - a.start[j]);
 }
 
 // The same apply for the outputs of bf16x3 trunk convolutions whose statistics are still per-tile partials (csrc/conv_x3.hip):
@@ -306,15 +295,13 @@ __global__ __launch_bounds__(256) void bn_apply_ws_kernel(ApplyWsArgs p) {
 }
 
 // BN -> ReLU -> MaxPool(3,2,1), NHWC.  relu(max(.)) == max(relu(.)); padding never wins (>= 1 valid tap).
-template <bool PLANES>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                               int n_img, int H, int W, int C, int OH, int OW,
                                                               int imgs_per_group, const float* __restrict__ mean,
                                                               const float* __restrict__ rstd,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta,
-                                                              const int* __restrict__ src_idx,
-                                                              unsigned short* __restrict__ planes, long long plane_stride) {
+                                                              const int* __restrict__ src_idx) {
     const int cq = C >> 2;
     const long long total = (long long)n_img * OH * OW * cq;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -348,14 +335,6 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) best[e] = fmaxf(best[e], 0.f);
         *(f32x4*)(y + i * 4) = best;
-        if constexpr (PLANES) {
-            mft_u32x2 p1, p2, p3;
-            mft_split4_bf16(best, p1, p2, p3);
-            unsigned short* q = planes + i * 4;
-            *(mft_u32x2*)(q) = p1;
-            *(mft_u32x2*)(q + plane_stride) = p2;
-            *(mft_u32x2*)(q + 2 * plane_stride) = p3;
-        }
     }
 }
 
@@ -778,9 +757,9 @@ extern "C" int mft_bn_apply(const float* x, int ldx, float* y, int ldy, int C, i
                             void* stream) {
     if (C % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (res && ldr % 4 != 0)) return MFT_EINVAL;
     ApplyArgs p{x, y, ldx, ldy, C, rows_per_group, n_groups, mean, rstd, gamma, beta, gb_group_stride,
-                res, ldr, res_mean, res_rstd, res_gamma, res_beta, act, slope, nullptr, 0};
+                res, ldr, res_mean, res_rstd, res_gamma, res_beta, act, slope};
     const long long total = (long long)n_groups * rows_per_group * (C / 4);
-    hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p);
     return mft_launch_status();
 }
 
@@ -793,7 +772,7 @@ extern "C" int mft_bn_apply_multi(const MftBnApplyJob* jobs, int n_jobs, void* s
             const MftBnApplyJob& jb = jobs[j0];
             if (jb.C % 4 != 0 || jb.ldx % 4 != 0 || jb.ldy % 4 != 0 || jb.rows_per_group < 1 || jb.n_groups < 1) return MFT_EINVAL;
             a.job[cnt] = ApplyArgs{jb.x, jb.y, jb.ldx, jb.ldy, jb.C, jb.rows_per_group, jb.n_groups, jb.mean, jb.rstd, jb.gamma, jb.beta, 0,
-                                   nullptr, 0, nullptr, nullptr, nullptr, nullptr, jb.act, jb.slope, nullptr, 0};
+                                   nullptr, 0, nullptr, nullptr, nullptr, nullptr, jb.act, jb.slope};
             a.start[cnt] = blocks;
             blocks += grid_for((long long)jb.n_groups * jb.rows_per_group * (jb.C / 4));
         }
@@ -869,20 +848,6 @@ extern "C" int mft_bn_apply_x3ws_fits(int C, int rows_per_group, int with_res_bn
     if (C % 4 != 0 || C > 1024 || rows_per_group < 128) return 0;
     return (size_t)4 * C * sizeof(float) + (with_res_bn ? 2 : 1) * mft_x3_stage_bytes_host(mft_x3_max_group_tiles(rows_per_group, 128), C) <=
            64 * 1024;
-}
-
-extern "C" int mft_bn_apply_planes(const float* x, int ldx, float* y, int ldy, unsigned short* planes, long long plane_stride,
-                                   int C, int rows_per_group, int n_groups, const float* mean, const float* rstd,
-                                   const float* gamma, const float* beta, long long gb_group_stride, const float* res, int ldr,
-                                   const float* res_mean, const float* res_rstd, const float* res_gamma,
-                                   const float* res_beta, int act, float slope, void* stream) {
-    if (C % 4 != 0 || ldx % 4 != 0 || (y && ldy % 4 != 0) || (res && ldr % 4 != 0) || !planes) return MFT_EINVAL;
-    if (plane_stride < (long long)n_groups * rows_per_group * C) return MFT_EINVAL;
-    ApplyArgs p{x, y, ldx, ldy, C, rows_per_group, n_groups, mean, rstd, gamma, beta, gb_group_stride,
-                res, ldr, res_mean, res_rstd, res_gamma, res_beta, act, slope, planes, plane_stride};
-    const long long total = (long long)n_groups * rows_per_group * (C / 4);
-    hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p);
-    return mft_launch_status();
 }
 
 // ------------------------------------------------------------------- stem cache as per-window (max, min) pairs
@@ -1042,28 +1007,16 @@ extern "C" int mft_bn_relu_pooled_gather_moments(const float* pmax, const float*
     return mft_launch_status();
 }
 
-extern "C" int mft_bn_relu_maxpool_gather_planes(const float* x, const int* src_idx, float* y, unsigned short* planes,
-                                                 long long plane_stride, int n_img, int H, int W, int C, int imgs_per_group,
-                                                 const float* mean, const float* rstd, const float* gamma, const float* beta,
-                                                 void* stream) {
+extern "C" int mft_bn_relu_maxpool_gather(const float* x, const int* src_idx, float* y, int n_img, int H, int W, int C,
+                                          int imgs_per_group, const float* mean, const float* rstd, const float* gamma,
+                                          const float* beta, void* stream) {
     if (C % 4 != 0) return MFT_EINVAL;
     if (imgs_per_group <= 0) imgs_per_group = n_img;
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     const long long total = (long long)n_img * OH * OW * (C / 4);
-    if (planes)
-        hipLaunchKernelGGL(bn_relu_maxpool_kernel<true>, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream,
-                           x, y, n_img, H, W, C, OH, OW, imgs_per_group, mean, rstd, gamma, beta, src_idx, planes, plane_stride);
-    else
-        hipLaunchKernelGGL(bn_relu_maxpool_kernel<false>, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream,
-                           x, y, n_img, H, W, C, OH, OW, imgs_per_group, mean, rstd, gamma, beta, src_idx, planes, plane_stride);
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream,
+                       x, y, n_img, H, W, C, OH, OW, imgs_per_group, mean, rstd, gamma, beta, src_idx);
     return mft_launch_status();
-}
-
-extern "C" int mft_bn_relu_maxpool_gather(const float* x, const int* src_idx, float* y, int n_img, int H, int W, int C,
-                                          int imgs_per_group, const float* mean, const float* rstd, const float* gamma,
-                                          const float* beta, void* stream) {
-    return mft_bn_relu_maxpool_gather_planes(x, src_idx, y, nullptr, 0, n_img, H, W, C, imgs_per_group, mean, rstd, gamma, beta,
-                                             stream);
 }
 
 extern "C" int mft_bn_relu_maxpool(const float* x, float* y, int n_img, int H, int W, int C, int imgs_per_group,

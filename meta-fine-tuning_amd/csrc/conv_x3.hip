@@ -38,8 +38,6 @@ struct X3Args {
     unsigned in_bytes, w_bytes;    // buffer-resource extents (< 2^31: out-of-range offsets are used as the zero-fill sentinel)
     int xcd_swizzle;
     int row_swz;                   // staging-row assignment that avoids LDS write bank conflicts
-    const unsigned short* in3;     // AP kernels: pre-split input planes [3][n_img*H*W][ldi] bf16 (written by mft_bn_apply_planes)
-    unsigned in_plane_bytes;
     float* stats_ws;               // optional [tiles_m][2][Cout][2]: per-tile (sum x, sum x^2) of the two BatchNorm groups a tile can touch
     int rows_per_group;            // >= BM when stats_ws is set
     int s1_rows;                   // conv_x3_s1_kernel: rows of the staged A image (BM + 2 halo pixels + 16 all-zero rows)
@@ -98,9 +96,6 @@ __device__ __forceinline__ void split4_h2(const f32x4 x, u32x2& p1, u32x2& p2) {
 }
 constexpr float X3_H2_LO_SCALE = 1.0f / 2048.f;
 
-// AP = true: the activation arrives already split into its three bf16 planes (the producing BatchNorm-apply / pooling kernel
-// split every element ONCE, instead of this loader re-splitting it for each of the 9 taps and each n-tile): the A path is
-// then the same plain 16-byte copy into LDS as the weight path, with no VALU work between the loads and the MFMAs.
 // DB = true: two LDS buffers and ONE barrier per K-step: the split + LDS store of tile kt+1 goes to the other buffer, so it
 // sits in the same basic block as the MFMAs of tile kt and the scheduler can issue it in their shadow (the single-buffer loop
 // has barrier - store - barrier between two MFMA blocks; PMC: waves 47 % issue-stalled / 24 % parked, matrix pipes 40 % busy).
@@ -111,13 +106,13 @@ constexpr float X3_H2_LO_SCALE = 1.0f / 2048.f;
 // XS: 64-byte LDS rows (no padding) with an XOR swizzle of the four 16-byte chunks of a row, chunk' = chunk ^ ((row >> 2) & 3):
 // fragment reads (16 lanes = 16 consecutive rows, one chunk) and staging writes (consecutive rows, whole rows) stay
 // conflict-free, and the tile takes 36 KB instead of 46 KB of LDS -> FOUR workgroups per CU instead of three.
-template <int BM, int BN, bool AP, bool DB, int HOIST = 0, int DBG = 0, bool XS = false, int NP = 3>
+template <int BM, int BN, bool DB, int HOIST = 0, int DBG = 0, bool XS = false, int NP = 3>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3 : 1))) void conv_x3_kernel(X3Args p) {
-    static_assert(NP == 3 || (NP == 2 && !AP && !DB && HOIST == 0 && DBG == 0 && !XS), "f16x2: the plain single-buffer form only");
+    static_assert(NP == 3 || (NP == 2 && !DB && HOIST == 0 && DBG == 0 && !XS), "f16x2: the plain single-buffer form only");
     constexpr int NACC = NP == 3 ? 1 : 2;
     constexpr int TM = BM / 64;           // 32-row blocks per wave (waves 2 x 2)
     constexpr int TN = BN / 64;
-    constexpr int PA = AP ? BM / 64 : BM / 32;   // A passes: fp32: 32 rows x 8 threads x float4; planes: 64 rows x 4 threads x 16 B
+    constexpr int PA = BM / 32;           // A passes: 32 rows per pass, 8 threads x float4 per row
     constexpr int PB = BN / 64;           // B passes: 64 rows per pass, 4 threads x 16 B per row and plane
     constexpr int RS = XS ? 32 : X3_RS;
     constexpr int A_PLANE = BM * RS;      // bf16 elements
@@ -154,25 +149,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3
     // Row owned by a thread in the staging passes.  LDS rows are 80 B = 20 banks apart, so four CONSECUTIVE rows written by one
     // 32-lane (ds_write_b64) or 16-lane (ds_write_b128) group wrap around the 64 banks and collide 2-way; rows 4 apart start
     // at banks 0/16/32/48.  Each group therefore owns rows {q, q+4, q+8, q+12} (PMC: 1/3 of the LDS-active cycles were conflicts).
-    const int g_id = AP ? tid >> 4 : tid >> 5;                 // 16-lane groups of 4 threads/row, 32-lane groups of 8 threads/row
-    const int g_rr = AP ? (tid >> 2) & 3 : (tid >> 3) & 3;
-    const int lrow = g_swz ? g_rr * 4 + (g_id & 3) + 16 * (g_id >> 2) : (AP ? tid >> 2 : tid >> 3);
-    const int c4 = AP ? (tid & 3) * 8 : (tid & 7) * 4;         // first channel of this thread's 16-byte piece
-    constexpr int RPP = AP ? 64 : 32;                          // rows per A pass
-    constexpr int ESZ = AP ? 2 : 4;                            // bytes per stored activation element
+    const int g_id = tid >> 5;                                 // 32-lane groups of 8 threads/row
+    const int g_rr = (tid >> 3) & 3;
+    const int lrow = g_swz ? g_rr * 4 + (g_id & 3) + 16 * (g_id >> 2) : tid >> 3;
+    const int c4 = (tid & 7) * 4;                              // first channel of this thread's 16-byte piece
     const int ohw = p.OH * p.OW;
     // Operands are fetched with raw buffer loads: one 32-bit byte offset per lane, and an offset beyond the buffer
     // (the sentinel 0x80000000) returns zeros -- that IS the zero padding of the convolution and of ragged tiles, so the
     // im2col gather costs a compare + select per row instead of 64-bit address arithmetic under divergent branches.
-    const __amdgpu_buffer_rsrc_t rA = AP ? __builtin_amdgcn_make_buffer_rsrc((void*)p.in3, 0, 3 * p.in_plane_bytes, 0x00020000)
-                                         : __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, p.w_bytes, 0x00020000);
     int a_off[PA];                 // byte offset of (img, ih0, iw0, channel c4); meaningful only with a valid tap
     int a_ih0[PA], a_iw0[PA];
     bool a_ok[PA];
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
-        const int m = m0 + lrow + RPP * j;
+        const int m = m0 + lrow + 32 * j;
         a_ok[j] = m < p.M;
         const int mm = a_ok[j] ? m : 0;
         const int img = mm / ohw;
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3
         const int oh = rem / p.OW, ow = rem - oh * p.OW;
         a_ih0[j] = oh * p.stride - p.pad;
         a_iw0[j] = ow * p.stride - p.pad;
-        a_off[j] = (((img * p.H + a_ih0[j]) * p.W + a_iw0[j]) * p.ldi + c4) * ESZ;
+        a_off[j] = (((img * p.H + a_ih0[j]) * p.W + a_iw0[j]) * p.ldi + c4) * 4;
     }
     const int bseg = tid & 3;
     const int brow = g_swz ? ((tid >> 2) & 3) * 4 + ((tid >> 4) & 3) + 16 * (tid >> 6) : tid >> 2;
@@ -206,8 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3
 
     // register stage: the operands of K-step kt+1 are in flight while kt is multiplied
     struct Stage {
-        f32x4 ra[AP ? 1 : PA];
-        u32x4 ra3[AP ? PA : 1][3];
+        f32x4 ra[PA];
         u32x4 rb[PB][NP];
     };
     Stage st0;
@@ -225,18 +216,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3
             if (t_ci0 == p.Cin) { t_ci0 = 0; if (++t_kw == p.KW) { t_kw = 0; ++t_kh; } }
         }
         const int ci0 = t_ci0, kh = t_kh, kw = t_kw;
-        const int tap_off = ((kh * p.W + kw) * p.ldi + ci0) * ESZ;
+        const int tap_off = ((kh * p.W + kw) * p.ldi + ci0) * 4;
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
             const bool ok = a_ok[j] && (unsigned)(a_ih0[j] + kh) < (unsigned)p.H && (unsigned)(a_iw0[j] + kw) < (unsigned)p.W;
             const unsigned voff = ok ? (unsigned)(a_off[j] + tap_off) : 0x80000000u;
-            if constexpr (AP) {
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-                    S.ra3[j][pl] = __builtin_amdgcn_raw_buffer_load_b128(rA, voff, pl * (int)p.in_plane_bytes, 0);
-            } else {
-                S.ra[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, voff, 0, 0));
-            }
+            S.ra[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, voff, 0, 0));
         }
 #pragma unroll
         for (int j = 0; j < PB; ++j)
@@ -249,15 +234,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 3
         unsigned short* Bs = As + NP * A_PLANE;
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
-            const int off = lo(lrow + RPP * j, c4);
+            const int off = lo(lrow + 32 * j, c4);
             if constexpr (NP == 2) {
                 u32x2 p1, p2;
                 split4_h2(S.ra[j], p1, p2);
                 *(u32x2*)(As + off) = p1;
                 *(u32x2*)(As + A_PLANE + off) = p2;
-            } else if constexpr (AP) {
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) *(u32x4*)(As + pl * A_PLANE + off) = S.ra3[j][pl];
             } else {
                 u32x2 p1, p2, p3;
                 if constexpr (DBG & 1) {
@@ -986,23 +968,23 @@ int g_x3_row_swz = 1;      // LDS layout (mft_debug_set_x3_tile(40 + v)): 0 80-b
 int g_x3_xcd = 1;          // XCD-aware tile order (mft_debug_set_x3_tile(20/21))
 int g_x3_min_lds_kb = 0;   // throttle: pad the workgroup's LDS so fewer fit per CU (mft_debug_set_x3_tile(100 + KB))
 
-template <int BM, int BN, bool AP, bool DB>
+template <int BM, int BN, bool DB>
 int launch_x3(X3Args p, hipStream_t s, int np = 3) {
     const int tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = p.Cout / BN;
     p.xcd_swizzle = g_x3_xcd;
     p.row_swz = g_x3_row_swz;
     if (np == 2) {                                  // f16x2: two planes per operand, the plain single-buffer kernel
-        if constexpr (!AP && !DB) {
+        if constexpr (!DB) {
             p.row_swz = g_x3_row_swz != 0;
             const size_t lds2 = (size_t)2 * (BM + BN) * X3_RS * sizeof(unsigned short);
-            hipLaunchKernelGGL((conv_x3_kernel<BM, BN, false, false, 0, 0, false, 2>), dim3((unsigned)(tiles_m * p.tiles_n)), dim3(256), lds2, s, p);
+            hipLaunchKernelGGL((conv_x3_kernel<BM, BN, false, 0, 0, false, 2>), dim3((unsigned)(tiles_m * p.tiles_n)), dim3(256), lds2, s, p);
             return mft_launch_status();
         }
         return MFT_EINVAL;
     }
 #ifdef MFT_EXPERIMENTS
-    const bool xs = g_x3_row_swz == 2 && !AP && !DB && g_x3_hoist == 0 && g_x3_dbg == 0;
+    const bool xs = g_x3_row_swz == 2 && !DB && g_x3_hoist == 0 && g_x3_dbg == 0;
 #else
     constexpr bool xs = false;
 #endif
@@ -1010,32 +992,32 @@ int launch_x3(X3Args p, hipStream_t s, int np = 3) {
 #ifdef MFT_EXPERIMENTS
     if ((size_t)g_x3_min_lds_kb * 1024 > lds) lds = (size_t)g_x3_min_lds_kb * 1024;
     if (xs) {
-        if constexpr (!AP && !DB) {
-            hipLaunchKernelGGL((conv_x3_kernel<BM, BN, false, false, 0, 0, true>), dim3((unsigned)(tiles_m * (p.Cout / BN))), dim3(256), lds, s,
+        if constexpr (!DB) {
+            hipLaunchKernelGGL((conv_x3_kernel<BM, BN, false, 0, 0, true>), dim3((unsigned)(tiles_m * (p.Cout / BN))), dim3(256), lds, s,
                                ([&] { X3Args q = p; q.tiles_n = p.Cout / BN; q.xcd_swizzle = g_x3_xcd; q.row_swz = 0; return q; })());
             return mft_launch_status();
         }
     }
-    auto kern = g_x3_hoist == 1 ? conv_x3_kernel<BM, BN, AP, DB, 1> : (g_x3_hoist == 2 ? conv_x3_kernel<BM, BN, AP, DB, 2> : conv_x3_kernel<BM, BN, AP, DB, 0>);
-    if (g_x3_dbg && !AP && !DB) {
+    auto kern = g_x3_hoist == 1 ? conv_x3_kernel<BM, BN, DB, 1> : (g_x3_hoist == 2 ? conv_x3_kernel<BM, BN, DB, 2> : conv_x3_kernel<BM, BN, DB, 0>);
+    if (g_x3_dbg && !DB) {
         switch (g_x3_dbg) {
-            case 1: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 1>; break;
-            case 2: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 2>; break;
-            case 4: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 4>; break;
-            case 8: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 8>; break;
-            case 12: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 12>; break;
-            case 13: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 13>; break;
-            case 16: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 16>; break;
-            case 28: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 28>; break;
-            case 32: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 32>; break;
-            case 34: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 34>; break;
-            case 36: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 36>; break;
-            case 33: kern = conv_x3_kernel<BM, BN, AP, DB, 0, 33>; break;
+            case 1: kern = conv_x3_kernel<BM, BN, DB, 0, 1>; break;
+            case 2: kern = conv_x3_kernel<BM, BN, DB, 0, 2>; break;
+            case 4: kern = conv_x3_kernel<BM, BN, DB, 0, 4>; break;
+            case 8: kern = conv_x3_kernel<BM, BN, DB, 0, 8>; break;
+            case 12: kern = conv_x3_kernel<BM, BN, DB, 0, 12>; break;
+            case 13: kern = conv_x3_kernel<BM, BN, DB, 0, 13>; break;
+            case 16: kern = conv_x3_kernel<BM, BN, DB, 0, 16>; break;
+            case 28: kern = conv_x3_kernel<BM, BN, DB, 0, 28>; break;
+            case 32: kern = conv_x3_kernel<BM, BN, DB, 0, 32>; break;
+            case 34: kern = conv_x3_kernel<BM, BN, DB, 0, 34>; break;
+            case 36: kern = conv_x3_kernel<BM, BN, DB, 0, 36>; break;
+            case 33: kern = conv_x3_kernel<BM, BN, DB, 0, 33>; break;
             default: break;
         }
     }
 #else
-    auto kern = conv_x3_kernel<BM, BN, AP, DB, 0>;
+    auto kern = conv_x3_kernel<BM, BN, DB, 0>;
 #endif
     if (lds > 64 * 1024) {                  // opt-in double-buffered / throttled forms only
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1158,23 +1140,21 @@ extern "C" int mft_debug_set_x3_tile(int t) {
 
 static int x3_dispatch(const float* in, int ldi, const unsigned short* w3, long long plane_elems, float* out, int ldo,
                        int n_img, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, float* stats_ws,
-                       int rows_per_group, void* stream, const unsigned short* in3 = nullptr, long long in_plane_elems = 0,
+                       int rows_per_group, void* stream,
                        const float* bn_ws = nullptr, const float* bn_gamma = nullptr, const float* bn_beta = nullptr,
                        float bn_eps = 0.f, int np = 3) {
     if (n_img <= 0 || Cin % 32 != 0 || Cout % 64 != 0 || ldi % 4 != 0 || (np != 3 && np != 2)) return MFT_EINVAL;
-    if (np == 2 && (in3 != nullptr || g_x3_tile > 1 || g_x3_db || g_x3_pp || g_x3_dbg || g_x3_hoist || g_x3_row_swz == 2 || g_x3_min_lds_kb ||
+    if (np == 2 && (g_x3_tile > 1 || g_x3_db || g_x3_pp || g_x3_dbg || g_x3_hoist || g_x3_row_swz == 2 || g_x3_min_lds_kb ||
                     g_x3_patch))
         return MFT_EINVAL;                     // f16x2 exists for the default 128x64 kernels only
     X3Args p;
     p.bn_ws = bn_ws; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta; p.bn_eps = bn_eps;
     p.bn_max_tiles = bn_ws ? mft_x3_max_group_tiles(rows_per_group, 128) : 0;
-    if (bn_ws != nullptr && (in3 != nullptr || !bn_gamma || !bn_beta || rows_per_group < 128 || KH != 3 || KW != 3 || stride != 1 ||
+    if (bn_ws != nullptr && (!bn_gamma || !bn_beta || rows_per_group < 128 || KH != 3 || KW != 3 || stride != 1 ||
                              pad != 1 || x3_s1_lds(128, 64, W, Cin, np) > X3_S1_LDS_3PER_CU ||
                              2 * mft_x3_stage_bytes_host(p.bn_max_tiles, Cin) >
                                  (size_t)np * (128 + 18) * X3_RS * sizeof(unsigned short)))
         return MFT_EINVAL;                     // the loader-side BatchNorm exists in the shared-tap kernel only, at full occupancy
-    p.in3 = in3;
-    p.in_plane_bytes = 0;
     p.stats_ws = stats_ws;
     p.rows_per_group = rows_per_group;
     p.in = in; p.w3 = w3; p.plane = plane_elems; p.out = out; p.ldi = ldi; p.ldo = ldo;
@@ -1189,17 +1169,6 @@ static int x3_dispatch(const float* in, int ldi, const unsigned short* w3, long 
     hipStream_t s = (hipStream_t)stream;
     int G = 0, R = 0;
     double eff = 0.0;
-    if (in3 != nullptr) {
-        // pre-split input planes: one launch, 32-bit byte offsets over the three planes
-        const long long need = (long long)n_img * H * W * ldi;
-        if (ldi % 8 != 0 || in_plane_elems < need || 3 * in_plane_elems * 2 >= 0x7fff0000LL || 3 * plane_elems * 2 >= 0x7fff0000LL)
-            return MFT_EINVAL;
-        if (stats_ws != nullptr && rows_per_group < 128) return MFT_EINVAL;
-        p.in_plane_bytes = (unsigned)(in_plane_elems * 2);
-        p.in_bytes = 0;
-        p.w_bytes = (unsigned)(3 * plane_elems * 2);
-        return launch_x3<128, 64, true, false>(p, (hipStream_t)stream);
-    }
 #ifdef MFT_EXPERIMENTS
     if (stats_ws == nullptr && g_x3_patch && KH == 3 && KW == 3 && stride == 1 && pad == 1 && ldi == Cin && ldo == Cout &&
         patch_geometry(H, W, &G, &R, &eff) && (g_x3_patch >= 2 || eff >= 0.9)) {
@@ -1247,14 +1216,14 @@ static int x3_dispatch(const float* in, int ldi, const unsigned short* w3, long 
                         x3_s1_lds(128, 64, W, 0, np) <= 64 * 1024;
         if (bn_ws != nullptr && !s1) return MFT_EINVAL;
         const int rc = s1 ? launch_x3_s1<128, 64>(q, s, np)
-                       : np == 2 ? launch_x3<128, 64, false, false>(q, s, 2)
-                       : (tile == 2 && Cout % 128 == 0) ? launch_x3<128, 128, false, false>(q, s)
-                       : (tile == 3)                  ? launch_x3<64, 64, false, false>(q, s)
+                       : np == 2 ? launch_x3<128, 64, false>(q, s, 2)
+                       : (tile == 2 && Cout % 128 == 0) ? launch_x3<128, 128, false>(q, s)
+                       : (tile == 3)                  ? launch_x3<64, 64, false>(q, s)
 #ifdef MFT_EXPERIMENTS
-                       : g_x3_db                      ? launch_x3<128, 64, false, true>(q, s)
+                       : g_x3_db                      ? launch_x3<128, 64, true>(q, s)
                        : (g_x3_pp && !g_x3_dbg)       ? launch_x3_pp<128, 64>(q, s)
 #endif
-                                                      : launch_x3<128, 64, false, false>(q, s);
+                                                      : launch_x3<128, 64, false>(q, s);
         if (rc != 0) return rc;
     }
     return 0;
@@ -1277,7 +1246,7 @@ extern "C" int mft_split_f16x2(const float* w, unsigned short* planes, long long
 extern "C" int mft_conv2d_nhwc_h2(const float* in, int ldi, const unsigned short* w2, long long plane_elems, float* out,
                                   int ldo, int n_img, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                                   int pad, void* stream) {
-    return x3_dispatch(in, ldi, w2, plane_elems, out, ldo, n_img, H, W, Cin, Cout, KH, KW, stride, pad, nullptr, 0, stream, nullptr, 0,
+    return x3_dispatch(in, ldi, w2, plane_elems, out, ldo, n_img, H, W, Cin, Cout, KH, KW, stride, pad, nullptr, 0, stream,
                        nullptr, nullptr, nullptr, 0.f, 2);
 }
 
@@ -1294,7 +1263,7 @@ static int x3_bnstats(int np, const float* in, int ldi, const unsigned short* w3
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
     const int R = imgs_per_group * OH * OW;
     const int rc = x3_dispatch(in, ldi, w3, plane_elems, out, ldo, n_img, H, W, Cin, Cout, KH, KW, stride, pad, stats_ws, R,
-                               stream, nullptr, 0, nullptr, nullptr, nullptr, 0.f, np);
+                               stream, nullptr, nullptr, nullptr, 0.f, np);
     if (rc != 0) return rc;
     if (mean == nullptr && rstd == nullptr) return g_x3_tile == 3 ? MFT_EINVAL : 0;     // partials only: the consumer merges them (128-row tiles)
     const int groups = n_img / imgs_per_group;
@@ -1330,7 +1299,7 @@ static int x3_bnin_bnstats(int np, const float* in, int ldi, const float* in_ws,
         (mean == nullptr) != (rstd == nullptr) || g_x3_tile == 3)
         return MFT_EINVAL;
     const int R = imgs_per_group * H * W;
-    const int rc = x3_dispatch(in, ldi, w3, plane_elems, out, ldo, n_img, H, W, Cin, Cout, 3, 3, 1, 1, stats_ws, R, stream, nullptr, 0,
+    const int rc = x3_dispatch(in, ldi, w3, plane_elems, out, ldo, n_img, H, W, Cin, Cout, 3, 3, 1, 1, stats_ws, R, stream,
                                in_ws, in_gamma, in_beta, eps, np);
     if (rc != 0 || mean == nullptr) return rc;
     hipLaunchKernelGGL(x3_stats_finalize_kernel, dim3((Cout + 63) / 64, n_img / imgs_per_group), dim3(64), 0, (hipStream_t)stream,
@@ -1352,21 +1321,4 @@ extern "C" int mft_conv2d_nhwc_h2_bnin_bnstats(const float* in, int ldi, const f
                                                float* stats_ws, float* mean, float* rstd, void* stream) {
     return x3_bnin_bnstats(2, in, ldi, in_ws, in_gamma, in_beta, w2, plane_elems, out, ldo, n_img, H, W, Cin, Cout, imgs_per_group, eps,
                            stats_ws, mean, rstd, stream);
-}
-
-extern "C" int mft_conv2d_nhwc_x3p_bnstats(const unsigned short* in_planes, long long in_plane_elems, int ldi,
-                                           const unsigned short* w3, long long plane_elems, float* out, int ldo, int n_img,
-                                           int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                           int imgs_per_group, float eps, float* stats_ws, float* mean, float* rstd,
-                                           void* stream) {
-    if (imgs_per_group <= 0 || n_img % imgs_per_group != 0 || stats_ws == nullptr || in_planes == nullptr) return MFT_EINVAL;
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    const int R = imgs_per_group * OH * OW;
-    const int rc = x3_dispatch(nullptr, ldi, w3, plane_elems, out, ldo, n_img, H, W, Cin, Cout, KH, KW, stride, pad, stats_ws, R,
-                               stream, in_planes, in_plane_elems);
-    if (rc != 0) return rc;
-    const int groups = n_img / imgs_per_group;
-    hipLaunchKernelGGL(x3_stats_finalize_kernel, dim3((Cout + 63) / 64, groups), dim3(64), 0, (hipStream_t)stream,
-                       (const float*)stats_ws, Cout, n_img * OH * OW, R, 128, eps, mean, rstd);
-    return mft_launch_status();
 }

@@ -332,10 +332,6 @@ class FinetuneEngine:
             ops._lib.lib().mft_stream_destroy(ctypes.c_void_p(self._raw_stream))
             self._raw_stream = None
             self.s_trunk = None
-            if getattr(self, "_raw_last", None) is not None:
-                ops._lib.lib().mft_stream_destroy(ctypes.c_void_p(self._raw_last))
-                self._raw_last = None
-                self.s_last = None
 
     def __del__(self):
         try:
@@ -407,27 +403,7 @@ class FinetuneEngine:
         # (trunk at the device's least priority, below torch's range: 68.2 / 68.1 / 67.7 vs 67.8 / 68.0 / 67.5 at normal)
         prio = cfg.trunk_priority
         self.s_trunk = None
-        self._raw_last = None
-        # CU partition (opt-in, MFT_TRUNK_CUS_PER_XCD = n): the frozen-trunk stream may use n of the 32 CUs of every XCD, the
-        # last-block stream the other 32 - n (hipExtStreamCreateWithCUMask; mask bit i -> XCD i % 8, CU i // 8).  A 3-read /
-        # 3-write stream keeps 93 % of its rate on 160 of the 256 CUs (tools/microbench/adam_cus.hip) while the matrix-bound
-        # trunk scales with its CU count.
-        n_tr = cfg.trunk_cus_per_xcd
-        if pipeline and 0 < n_tr < 32:
-            def masked(bits):
-                words = (ctypes.c_uint * 8)()
-                for b in bits:
-                    words[b // 32] |= (1 << (b % 32))
-                out = ctypes.c_void_p()
-                ops._lib.check(ops._lib.lib().mft_stream_create_cumask(ctypes.cast(words, ctypes.c_void_p), 8, ctypes.byref(out)),
-                               "mft_stream_create_cumask")
-                return out.value
-            self._raw_stream = masked([i for i in range(256) if (i // 8) >= 32 - n_tr])
-            self.s_trunk = torch.cuda.ExternalStream(self._raw_stream, device=self.dev)
-            if not cfg.trunk_cus_only:      # (=1: only the trunk is confined; the last block may run anywhere)
-                self._raw_last = masked([i for i in range(256) if (i // 8) < 32 - n_tr])
-                self.s_last = torch.cuda.ExternalStream(self._raw_last, device=self.dev)
-        elif pipeline and prio > 0:              # below torch's range: a HIP stream at the device's least priority
+        if pipeline and prio > 0:              # below torch's range: a HIP stream at the device's least priority
             out = ctypes.c_void_p()
             with torch.cuda.device(self.dev):
                 ops._lib.check(ops._lib.lib().mft_stream_create_priority(prio, ctypes.byref(out), None), "mft_stream_create_priority")
@@ -435,8 +411,7 @@ class FinetuneEngine:
             self.s_trunk = torch.cuda.ExternalStream(out.value, device=self.dev)
         elif pipeline:
             self.s_trunk = torch.cuda.Stream(device=self.dev, priority=prio)
-        if self._raw_last is None:
-            self.s_last = torch.cuda.Stream(device=self.dev, priority=cfg.last_priority) if pipeline else None
+        self.s_last = torch.cuda.Stream(device=self.dev, priority=cfg.last_priority) if pipeline else None
         px = image_size * image_size * 3
         self.Xs = torch.empty((self.E * self.n_total, px), device=self.dev)       # support store, NHWC rows
         self.Xall = torch.empty((self.E * self.n_all, image_size, image_size, 3), device=self.dev)
@@ -450,13 +425,10 @@ class FinetuneEngine:
             # (42 x 42 x 64 per image) although the default keeps the pooled (max, min) pair -- half of it -- so 20-shot at
             # E = 128 (115.6 GB full-resolution, 58 GB pooled) silently lost its stem cache and ran slower than E = 96
             # (19.9 vs 22.0 episodes/s, profiles/r04_f_other_configs.txt; round-4 verdict weak 9).
-            pooled_pref = False if Fn.X3_PLANES else None
-            need = Fn.StemCache.bytes_needed(self.E * self.n_total, image_size, pooled=pooled_pref)
+            need = Fn.StemCache.bytes_needed(self.E * self.n_total, image_size)
             total = torch.cuda.get_device_properties(self.dev).total_memory
             stem_cache = need <= 0.35 * total
-        # (the opt-in pre-split-planes trunk reads the full-resolution cache; the default is the pooled (max, min) form)
-        self._stem_pooled = False if Fn.X3_PLANES else None
-        self.stem = Fn.StemCache(self.W, self.E * self.n_total, image_size, self.dev, pooled=self._stem_pooled) if stem_cache else None
+        self.stem = Fn.StemCache(self.W, self.E * self.n_total, image_size, self.dev) if stem_cache else None
         self.fuse_next = fuse_next_policy(self._fuse_next_setting, self.E, self.stem is not None, image_size, self.W.f16x2)
 
     # ------------------------------------------------------------------ ingest
@@ -838,7 +810,7 @@ class FinetuneEngine:
             if need > 0.8 * free:
                 return                                           # not enough room for a second support store + stem cache
             self._pre_bufs = {"Xs": torch.empty_like(self.Xs),
-                              "stem": Fn.StemCache(self.W, self.E * self.n_total, self.size, self.dev, pooled=self._stem_pooled),
+                              "stem": Fn.StemCache(self.W, self.E * self.n_total, self.size, self.dev),
                               "stream": torch.cuda.Stream(device=self.dev)}
         b = self._pre_bufs
         sp = b["stream"]

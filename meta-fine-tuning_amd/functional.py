@@ -23,10 +23,6 @@ from . import settings
 # 64x64-tile kernel does: 70.8 / 71.5 / 69.4 vs 71.0 / 71.4 / 71.1 episodes/s -- off by default.
 FUSED_DGRAD = settings.current().fused_dgrad
 FUSED_LAST_BLOCK = settings.current().fused_last_block   # conv + BatchNorm fusions of the adapted block (csrc/skinny.hip)
-# opt-in: trunk activations travel pre-split into bf16x3 planes between the x3 convolutions.  Bit-identical, but measured
-# SLOWER (66.5 vs 69.0 episodes/s): the convolutions are not bound by the in-loader split (161 vs 160 us standalone) while the
-# producers write 1.5x the bytes -- kept for the record (tests/test_engine_gpu.py::test_presplit_activation_planes_are_bit_identical)
-X3_PLANES = settings.current().x3_planes
 X3_FUSED_STATS = settings.current().x3_fused_stats   # BatchNorm statistics from the bf16x3 convolution epilogue
 # frozen trunk blocks without helper launches: statistics stay per-tile partials that each consumer merges itself, BN1 + ReLU is
 # applied by C2's loader, the stem's batch statistics are combined inside the pooled gather (12-13 launches per lockstep step
@@ -38,10 +34,6 @@ X3_FOLD_BN = settings.current().x3_fold_bn
 TRUNK_F16X2 = settings.current().trunk_f16x2
 TRAIN_X3 = settings.current().train_x3            # meta-training: large 3x3 layers on the bf16x3 kernels (ResNet10Weights.train_planes)
 TRAIN_X3_MIN_ROWS = settings.current().train_x3_min_rows
-# fused next-step forward (engine.fuse_next), opt-in variant: only trunk.7.C2's launch is the fused walking kernel, C1 / shortcut keep
-# the plain gradient + Adam launches + one entry launch (last_block_backward).  Alone that chain is 100 us shorter, in situ it is
-# slower: 87.2 vs 88.8-89.0 episodes/s (profiles/r04_d_fuse_c2_only_ab.txt) -- default 0 = all three layers fused
-FUSE_NEXT_C2_ONLY = settings.current().fuse_next_c2_only
 F16X2_BOUND = 3.0e4              # < 65504 with a factor 2 in hand
 F16X2_FLOOR = 2.0 ** -10          # typical operand magnitude that keeps the pieces normal fp16 numbers
 F16X2_MAX_ROWS = 1 << 20         # largest BatchNorm group (images x pixels) the bound is proven for (engine: 100 x 21 x 21 = 44,100)
@@ -158,7 +150,7 @@ class ResNet10Weights:
         self.conv3 = {}
         self.f16x2_rows = F16X2_MAX_ROWS if max_rows is None else max(int(max_rows), 1)
         if f16x2 is None:
-            f16x2 = bool(x3) and TRUNK_F16X2 and not X3_PLANES and f16x2_safe(sd, prefix, self.f16x2_rows)
+            f16x2 = bool(x3) and TRUNK_F16X2 and f16x2_safe(sd, prefix, self.f16x2_rows)
         self.f16x2 = bool(f16x2)
         split = ops.split_weight_h2 if self.f16x2 else ops.split_weight_x3
         self.bn = {}
@@ -321,7 +313,7 @@ class StemCache:
     def __init__(self, W, n_slots, H, device, chunk=8192, pooled=None):
         """``pooled`` (default: env MFT_STEM_POOLED, on): keep only the per-window maxima / minima of the raw stem output
         (csrc/bn.hip, exact: the BatchNorm affine is monotone per channel) -- half the memory of the full-resolution cache and a
-        quarter to a half of the bytes per gather; the full-resolution form (``c0``) exists for the planes / test paths."""
+        quarter to a half of the bytes per gather; the full-resolution form (``c0``) exists for the test paths."""
         self.W = W
         self.n_slots = n_slots
         self.OH = (H + 6 - 7) // 2 + 1
@@ -384,15 +376,15 @@ class StemCache:
                 ops._lib.check(lib.mft_pool_window_minmax(ops._p(c0), ops._p(self.pmax[i:j]), ops._p(self.pmin[i:j]), j - i,
                                                           self.OH, self.OH, 64, ops._stream()), "mft_pool_window_minmax")
 
-    def gather(self, idx, n, m, s, g, b, ipg, out, planes=None):
+    def gather(self, idx, n, m, s, g, b, ipg, out):
         """BN + ReLU + MaxPool of images idx with the mini-batch statistics (m, s) -> out [n, PH, PH, 64]."""
-        if self.pooled and planes is None:
+        if self.pooled:
             ops._lib.check(ops._lib.lib().mft_bn_relu_pooled_gather(ops._p(self.pmax), ops._p(self.pmin), ops._p(idx), ops._p(out), n,
                                                                     self.PH, self.PH, 64, ipg, ops._p(m), ops._p(s), ops._p(g),
                                                                     ops._p(b), ops._stream()), "mft_bn_relu_pooled_gather")
             return out
         assert self.c0 is not None, "this path needs the full-resolution stem cache (StemCache(pooled=False))"
-        return ops.bn_relu_maxpool_gather(self.c0, idx, n, m, s, g, b, ipg, out=out, planes=planes)
+        return ops.bn_relu_maxpool_gather(self.c0, idx, n, m, s, g, b, ipg, out=out)
 
     def gather_moments(self, idx, n, g, b, ipg, out, stats=None):
         """gather() with the mini-batch statistics combined from the cached per-image moments in the same launch."""
@@ -422,29 +414,11 @@ def resnet10_trunk(W, x, arena, ipg, upto=7, running=None, tag="t", stem=None, f
         n = idx.numel()
         groups = n // ipg
         PH = (cache.OH + 2 - 3) // 2 + 1
-        fold = X3_FOLD_BN and cache.pooled and not X3_PLANES and running is None and fixed is None
+        fold = X3_FOLD_BN and cache.pooled and running is None and fixed is None
         if not fold:
             m = arena.get(tag + ".bn0.mean", (groups, 64))
             s = arena.get(tag + ".bn0.rstd", (groups, 64))
             ops.bn_combine_moments(cache.mean, cache.m2, idx, cache.OH * cache.OH, ipg, groups, mean=m, rstd=s)
-        if (X3_PLANES and cache.c0 is not None and X3_FUSED_STATS and upto == 7 and running is None and fixed is None and ipg * ((PH + 3) // 4) ** 2 >= 128
-                and all(("trunk.%d.C1" % i) in W.conv3 for i in (4, 5, 6))):
-            # frozen trunk on pre-split activations: each tensor between two bf16x3 convolutions is written once as three
-            # bf16 planes by its producer (pool / BatchNorm-apply) instead of being re-split by every consumer tile
-            ap = arena.get(tag + ".p0p", (3, n * PH * PH, 64), torch.int16)
-            a = cache.gather(idx, n, m, s, g, b, ipg, arena.get(tag + ".p0", (n, PH, PH, 64)), planes=ap)
-            shape = (n, PH, PH, 64)
-            for bi in (4, 5, 6):
-                cin, cout, stride = STAGES[bi]
-                p = "trunk.%d" % bi
-                mode = "f32" if bi == 6 else "planes"
-                r = simple_block(W, p, a if bi == 4 else None, arena, ipg, cin, cout, stride, None, tag + "." + p, xp=ap,
-                                 xshape=shape, out_mode=mode)
-                if mode == "f32":
-                    return r
-                _, ap = r
-                OHb = (shape[1] + 2 - 3) // stride + 1
-                shape = (n, OHb, OHb, cout)
         if fold:
             a = cache.gather_moments(idx, n, g, b, ipg, arena.get(tag + ".p0", (n, PH, PH, 64)))
         else:
@@ -481,16 +455,13 @@ def _bn_small(arena, tag, x1, g1, b1, rows, groups, C, gbs, out, x2=None, g2=Non
 
 
 def simple_block(W, p, x, arena, ipg, cin, cout, stride, running=None, tag="b", slab=None, tape=None, pooled=None, fixed=None,
-                 xp=None, xshape=None, out_mode="f32", stats_out=None):
+                 stats_out=None):
     """SimpleBlock.forward (backbone.py:251-261).  ``slab``: per-group parameters (LastBlockSlab) or None for W's.
     ``pooled``: optional [n, cout] buffer; filled with the global average pool of the block output when the fused
     small-group path applies (``tape['pooled']`` is then True and the caller skips its own pooling launch).
-    ``xp``: the block input pre-split into bf16x3 planes (int16 [3, n*H*W, cin]); frozen x3 blocks then keep their internal
-    activation in planes too, and ``out_mode`` ("f32" | "planes" | "both") selects the form(s) of the block output
-    (returns ``out`` or ``(out, out_planes)``; ``x`` may be None when only its planes are needed, with ``xshape`` = its shape).
     ``stats_out`` (small-group slab path): {"bn1" | "bn2" | "bns": (mean, rstd) [groups, cout]} -- where the three BatchNorms'
     batch statistics are written instead of arena buffers (the caller advances the running statistics from them afterwards)."""
-    n, H, Wd, _ = x.shape if x is not None else xshape
+    n, H, Wd, _ = x.shape
     groups = n // ipg
     OH = (H + 2 - 3) // stride + 1
 
@@ -582,44 +553,11 @@ def simple_block(W, p, x, arena, ipg, cin, cout, stride, running=None, tag="b", 
         mm, ss_ = _bn_stats4(arena, stag, o, ipg, groups, run(p + bnname), fix(p + bnname))
         return o, mm, ss_
 
-    if (X3_FOLD_BN and xp is None and fuse_stats and tape is None and out_mode == "f32"
+    if (X3_FOLD_BN and fuse_stats and tape is None
             and all((p + nm) in w3 for nm in ((".C1", ".C2", ".shortcut") if cin != cout else (".C1", ".C2")))):
         r = _frozen_block_folded(W, p, x, arena, ipg, cin, cout, stride, tag)
         if r is not None:
             return r
-
-    if xp is not None and fuse_stats and tape is None and all((p + nm) in w3 for nm in ((".C1", ".C2", ".shortcut") if cin != cout
-                                                                                      else (".C1", ".C2"))):
-        # pre-split activation chain: every x3 convolution reads bf16 planes written once by its producer
-        def conv_bn_p(name, inp_p, h_in, k, s, pd, obuf, stag):
-            nws = int(ops._lib.lib().mft_conv2d_x3_stats_ws_floats(n, h_in, h_in, cout, k, k, s, pd))
-            ws = arena.get("x3.statws", (max(nws, 1 << 20),)) if nws <= (1 << 20) else arena.get(stag + ".statws", (nws,))
-            mean = arena.get(stag + ".mean", (groups, cout))
-            rstd = arena.get(stag + ".rstd", (groups, cout))
-            return ops.conv2d_x3p_bnstats(inp_p, n, h_in, h_in, w3[p + name], cout, k, k, s, pd, ipg, obuf, ws, mean, rstd)
-
-        c1, m1, s1 = conv_bn_p(".C1", xp, H, 3, stride, 1, arena.get(tag + ".c1", (n, OH, OH, cout)), tag + ".bn1")
-        r1p = arena.get(tag + ".r1p", (3, n * OH * OH, cout), torch.int16)
-        ops.bn_apply(c1.view(-1, cout), cout, rows, groups, m1, s1, g1, b1, act=ops.ACT_RELU, fma_affine=True, gb_group_stride=gbs, planes=r1p,
-                     write_y=False)
-        c2, m2, s2 = conv_bn_p(".C2", r1p, OH, 3, 1, 1, arena.get(tag + ".c2", (n, OH, OH, cout)), tag + ".bn2")
-        want_f32 = out_mode in ("f32", "both")
-        out = arena.get(tag + ".out", (n * OH * OH, cout)) if want_f32 else None
-        outp = arena.get(tag + ".outp", (3, n * OH * OH, cout), torch.int16) if out_mode in ("planes", "both") else None
-        if cin != cout:
-            sc, ms, ss = conv_bn_p(".shortcut", xp, H, 1, stride, 0, arena.get(tag + ".sc", (n, OH, OH, cout)), tag + ".bns")
-            res, res_bn = sc.view(-1, cout), (ms, ss, gs, bs)
-        else:
-            res, res_bn = x.view(-1, cin), None
-        if outp is not None:
-            ops.bn_apply(c2.view(-1, cout), cout, rows, groups, m2, s2, g2, b2, act=ops.ACT_RELU, fma_affine=True, res=res, res_bn=res_bn, out=out,
-                         gb_group_stride=gbs, planes=outp, write_y=want_f32)
-        else:
-            ops.bn_apply(c2.view(-1, cout), cout, rows, groups, m2, s2, g2, b2, act=ops.ACT_RELU, fma_affine=True, res=res, res_bn=res_bn, out=out,
-                         gb_group_stride=gbs)
-        out = out.view(n, OH, OH, cout) if out is not None else None
-        return out if out_mode == "f32" else (out, outp)
-    assert out_mode == "f32" or xp is None or not fuse_stats, "planes output requested outside the pre-split chain"
 
     c1, m1, s1 = conv_bn(".C1", ".BN1", x, c1w, 3, stride, 1, arena.get(tag + ".c1", (n, OH, OH, cout)), tag + ".bn1")
     r1 = ops.bn_apply(c1.view(-1, cout), cout, rows, groups, m1, s1, g1, b1, act=ops.ACT_RELU, fma_affine=fuse_stats,
@@ -864,34 +802,14 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
         adam_tail()
         kw = dict(lr=lr, hyper=hyper)
         fw = x_next is not None
-        ok = hybrid = False
-        if FUSE_NEXT_C2_ONLY and FUSED_LAST_BLOCK and groups > ops.SMALL_GROUPS:
-            # Only trunk.7.C2 takes the fused launch (opt-in).  Alone, C1's and the shortcut's fused launches are 154 + 50 us longer
-            # than the plain gradient + Adam launches and save the 137 us entry launch; the entry forward of step t+1 then reads the
-            # updated C1 / shortcut weights once more (1.3 of the 14.7 MB per episode).  In situ the trunk stream finishes no earlier
-            # beside the plain launches than beside the walking kernel, and the step is 1.7 % slower.
-            wgrad(x, dsc, "scw", 1, 2, 0)
-            wgrad(x, dc1, "c1w", 3, 2, 1)
-            hybrid = ok = True
-            if fw:
-                wait_next_once()
-                rc = lib.mft_block_entry_small_forward(
-                    ops._p(x_next), x_next.shape[-1], ops._p(params.c1w), params.c1w.shape[1] * params.c1w.shape[2], ops._p(params.scw),
-                    params.scw.shape[1] * params.scw.shape[2], ops._p(tn["c1"]), ops._p(tn["r1"]), ops._p(tn["sc"]), n, x_next.shape[1],
-                    x_next.shape[2], x_next.shape[-1], C, 2, ipg, ops._p(params.bn1g), ops._p(params.bn1b), C, ops._p(tn["m1"]),
-                    ops._p(tn["s1"]), ops.BN_EPS, ops._stream())
-                if rc == ops._lib.MFT_EINVAL:
-                    raise RuntimeError("block entry launch outside its domain after next_forward_ok accepted the shape")
-                ops._lib.check(rc, "mft_block_entry_small_forward")
-        if not hybrid:
-            if fw:
-                wait_next_once()
-            ok = ops.wgrad_adam_next_forward(x, dsc, params.scw, m_.scw, v_.scw, 1, 1, 2, 0, st, ipg, x_next=x_next, mode=ops.WF_RAW,
-                                             raw=tn["sc"] if fw else None, **kw)
-            ok = ok and ops.wgrad_adam_next_forward(x, dc1, params.c1w, m_.c1w, v_.c1w, 3, 3, 2, 1, st, ipg, x_next=x_next,
-                                                    mode=ops.WF_ENTRY, raw=tn["c1"] if fw else None, act=tn["r1"] if fw else None,
-                                                    gamma=params.bn1g, beta=params.bn1b, gbs=C, mean=tn["m1"] if fw else None,
-                                                    rstd=tn["s1"] if fw else None, **kw)
+        if fw:
+            wait_next_once()
+        ok = ops.wgrad_adam_next_forward(x, dsc, params.scw, m_.scw, v_.scw, 1, 1, 2, 0, st, ipg, x_next=x_next, mode=ops.WF_RAW,
+                                         raw=tn["sc"] if fw else None, **kw)
+        ok = ok and ops.wgrad_adam_next_forward(x, dc1, params.c1w, m_.c1w, v_.c1w, 3, 3, 2, 1, st, ipg, x_next=x_next,
+                                                mode=ops.WF_ENTRY, raw=tn["c1"] if fw else None, act=tn["r1"] if fw else None,
+                                                gamma=params.bn1g, beta=params.bn1b, gbs=C, mean=tn["m1"] if fw else None,
+                                                rstd=tn["s1"] if fw else None, **kw)
         ok = ok and ops.wgrad_adam_next_forward(r1, dc2, params.c2w, m_.c2w, v_.c2w, 3, 3, 1, 1, st, ipg,
                                                 x_next=tn["r1"] if fw else None, mode=ops.WF_EXIT, raw=tn["c2"] if fw else None,
                                                 act=tn["out"] if fw else None, gamma=params.bn2g, beta=params.bn2b, gbs=C,

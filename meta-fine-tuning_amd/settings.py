@@ -43,18 +43,14 @@ KNOBS = (
     ("trunk_chunk", "MFT_TRUNK_CHUNK", _opt_int, None, "inner steps per frozen-trunk launch set (None: 32 at E = 1, else 1)"),
     ("trunk_priority", "MFT_TRUNK_PRIORITY", int, 1, "HIP priority of the frozen-trunk stream (1 = the device's least)"),
     ("last_priority", "MFT_LAST_PRIORITY", int, -1, "torch priority of the last-block stream"),
-    ("trunk_cus_per_xcd", "MFT_TRUNK_CUS_PER_XCD", int, 0, "CU-masked streams: CUs per XCD for the trunk stream (0 = no partition; measured slower)"),
-    ("trunk_cus_only", "MFT_TRUNK_CUS_ONLY", _flag, False, "with trunk_cus_per_xcd: confine only the trunk stream"),
     ("debug_skip_trunk", "MFT_DEBUG_SKIP_TRUNK", _flag, False, "measurement aid: reuse one cached trunk output (results are WRONG)"),
     ("adapt_graph", "MFT_ADAPT_GRAPH", _flag, True, "adapt_last_block: replay the meta-fine-tuning inner loop from one hipGraph"),
     ("adapt_batched_trunk", "MFT_ADAPT_BATCHED_TRUNK", _flag, True, "adapt_last_block: frozen trunk of all steps as two grouped passes"),
     # ---- kernel-path selection (functional.py)
     ("fused_dgrad", "MFT_FUSED_DGRAD", _flag, False, "one-pass trunk.7.C2 weight gradient + Adam + data gradient (measured slower in the step)"),
-    ("x3_planes", "MFT_X3_PLANES", _flag, False, "trunk activations pre-split into bf16x3 planes (measured slower)"),
     ("x3_fused_stats", "MFT_X3_FUSED_STATS", _flag, True, "BatchNorm statistics from the split-precision convolution epilogue"),
     ("x3_fold_bn", "MFT_X3_FOLD_BN", _flag, True, "frozen blocks without helper launches (per-tile partials merged by the consumers)"),
     ("trunk_f16x2", "MFT_TRUNK_F16X2", _flag, True, "frozen trunk.4-6 on two fp16 pieces per operand (0: three bf16 pieces)"),
-    ("fuse_next_c2_only", "MFT_FUSE_NEXT_C2_ONLY", _flag, False, "only trunk.7.C2's launch fused (measured slower)"),
     ("stem_pooled", "MFT_STEM_POOLED", _flag, True, "stem cache keeps per-window (max, min) instead of the full-resolution output"),
     ("stem_fused_fill", "MFT_STEM_FUSED_FILL", _flag, True, "stem cache filled by ONE launch (convolution + moments + window min/max; 0: three launches through a full-resolution buffer)"),
     ("stem_chunk", "MFT_STEM_CHUNK", _opt_int, None, "images per stem-cache fill launch (None: StemCache's default)"),
@@ -96,17 +92,13 @@ class Settings:
     trunk_chunk: "int | None" = None
     trunk_priority: int = 1
     last_priority: int = -1
-    trunk_cus_per_xcd: int = 0
-    trunk_cus_only: bool = False
     debug_skip_trunk: bool = False
     adapt_graph: bool = True
     adapt_batched_trunk: bool = True
     fused_dgrad: bool = False
-    x3_planes: bool = False
     x3_fused_stats: bool = True
     x3_fold_bn: bool = True
     trunk_f16x2: bool = True
-    fuse_next_c2_only: bool = False
     stem_pooled: bool = True
     stem_fused_fill: bool = True
     stem_chunk: "int | None" = None
@@ -149,8 +141,8 @@ class Settings:
         s = cls(**kw)
         if s.train_source not in ("pool", "synthetic"):
             raise ValueError("MFT_TRAIN_SOURCE=%r: expected pool or synthetic" % (s.train_source,))
-        if s.image_size < 32 or not 0 <= s.trunk_cus_per_xcd < 32:
-            raise ValueError("MFT_IMAGE_SIZE / MFT_TRUNK_CUS_PER_XCD out of range")
+        if s.image_size < 32:
+            raise ValueError("MFT_IMAGE_SIZE out of range")
         return s
 
 
@@ -171,8 +163,8 @@ def current():
 # Knobs that modules freeze into module-level constants when they are first imported (a later change of the variable has no effect
 # in that process); every other knob is read live through ``current()`` at the point of use.
 IMPORT_TIME = frozenset((
-    "debug_skip_trunk", "adapt_graph", "adapt_batched_trunk", "fused_dgrad", "fused_last_block", "x3_planes", "x3_fused_stats",
-    "x3_fold_bn", "trunk_f16x2", "train_x3", "train_x3_min_rows", "fuse_next_c2_only", "fused_pair_mlp", "pair_f16x2", "pair_rk_rows", "gemm_rk_rows", "pair_mlp_gb", "wgrad_batch",
+    "debug_skip_trunk", "adapt_graph", "adapt_batched_trunk", "fused_dgrad", "fused_last_block", "x3_fused_stats",
+    "x3_fold_bn", "trunk_f16x2", "train_x3", "train_x3_min_rows", "fused_pair_mlp", "pair_f16x2", "pair_rk_rows", "gemm_rk_rows", "pair_mlp_gb", "wgrad_batch",
     "train_graph", "small_groups", "wf_xcd",
 ))
 assert IMPORT_TIME <= set(k[0] for k in KNOBS), IMPORT_TIME - set(k[0] for k in KNOBS)
