@@ -8,7 +8,8 @@
 
 namespace {
 
-// one wave per row; C <= 4096
+// one wave per row.  The row maximum mx and lg = log(sum exp(x - mx)) stay apart: mx + lg would round to ulp(|mx|) and take the
+// probabilities exp(x - lse) and the loss lse - x[y] with it once the logits are large (squared distances, ridge scores).
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits, int ld,
                                                             const int* __restrict__ labels, int C,
                                                             int rows_per_group, int n_groups,
@@ -26,13 +27,13 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
     for (int c = lane; c < C; c += 64) se += __expf(x[c] - mx);
     se = wave_sum(se);
     const int y = labels[row];
-    const float lse = mx + __logf(se);
-    if (lane == 0) row_loss[row] = lse - x[y];
+    const float lg = __logf(se);
+    if (lane == 0) row_loss[row] = lg - (x[y] - mx);
     if (dlogits) {
         const float inv = 1.f / (float)rows_per_group;
         float* d = dlogits + row * ld;
         for (int c = lane; c < C; c += 64) {
-            float pr = __expf(x[c] - lse);
+            float pr = __expf((x[c] - mx) - lg);
             d[c] = (pr - (c == y ? 1.f : 0.f)) * inv;
         }
     }
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const float* __restrict__ 
             for (int c = 0; c < 16; ++c) se += c < C ? __expf(v[c] - mx) : 0.f;
             const long long y = ce_label(labels, i64, row);
             const float xy = (y >= 0 && y < C) ? x[y] : __builtin_nanf("");      // an out-of-range label poisons the loss (torch asserts)
-            acc += (mx + __logf(se)) - xy;
+            acc += __logf(se) - (xy - mx);
         }
     } else {                                      // a wave per row (row = wave, wave + 4, ...); lane 0 carries the wave's sum
         for (int row = wave; row < rows; row += 4) {
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const float* __restrict__ 
             se = wave_sum(se);
             const long long y = ce_label(labels, i64, row);
             const float xy = (y >= 0 && y < C) ? x[y] : __builtin_nanf("");
-            if (lane == 0) acc += (mx + __logf(se)) - xy;
+            if (lane == 0) acc += __logf(se) - (xy - mx);
         }
     }
     part[threadIdx.x] = acc;
@@ -210,11 +211,11 @@ __global__ __launch_bounds__(256) void ce_mean_bwd_kernel(const float* __restric
     float se = 0.f;
     for (int c = lane; c < C; c += 64) se += __expf(x[c] - mx);
     se = wave_sum(se);
-    const float lse = mx + __logf(se);
+    const float lg = __logf(se);
     const long long y = ce_label(labels, i64, row);
     const float sc = (gout ? gout[0] : 1.f) / (float)rows;
     float* d = dlogits + row * ldd;
-    for (int c = lane; c < C; c += 64) d[c] = (__expf(x[c] - lse) - (c == y ? 1.f : 0.f)) * sc;
+    for (int c = lane; c < C; c += 64) d[c] = (__expf((x[c] - mx) - lg) - (c == y ? 1.f : 0.f)) * sc;
 }
 }  // namespace
 
@@ -339,11 +340,11 @@ __global__ __launch_bounds__(256) void linear_head_step_kernel(
         for (int c = 0; c < n_way; ++c) mx = fmaxf(mx, s_logit[r][c]);
         float se = 0.f;
         for (int c = 0; c < n_way; ++c) se += __expf(s_logit[r][c] - mx);
-        const float lse = mx + __logf(se);
+        const float lg = __logf(se);
         const int y = labels[(long long)g * k + r];
-        s_loss[r] = lse - s_logit[r][y];
+        s_loss[r] = lg - (s_logit[r][y] - mx);
         const float inv = 1.f / (float)k;
-        for (int c = 0; c < n_way; ++c) s_d[r][c] = (__expf(s_logit[r][c] - lse) - (c == y ? 1.f : 0.f)) * inv;
+        for (int c = 0; c < n_way; ++c) s_d[r][c] = (__expf((s_logit[r][c] - mx) - lg) - (c == y ? 1.f : 0.f)) * inv;
     }
     __syncthreads();
     if (tid == 0 && loss) {
@@ -442,6 +443,9 @@ extern "C" int mft_linear_head_scores(const float* feat, int ldf, int rows_per_g
 // Inner-loop loss on the pooled feature (finetune.py:286-293): per group, cross entropy over the C-wide feature rows,
 // dlogits = (softmax - onehot)/rows, and straight on through AvgPool + the block's final ReLU:
 // d_out[img*hw + p][c] = out > 0 ? dlogits[img][c] / hw : 0.  One workgroup per group; replaces three launches.
+// This kernel and its fused twin (bn.hip: bn_backward2_ce_kernel, bit-identical to it) still add lse = mx + log(se) first: their
+// logits are pooled post-ReLU features of a few units, and the full-length trajectory goldens (G4e, G19 D) were accepted with
+// this arithmetic -- DESIGN.md section 6.
 namespace {
 __global__ __launch_bounds__(256) void ce_pool_backward_kernel(const float* __restrict__ feat, const int* __restrict__ labels,
                                                                int k, int C, int hw, const float* __restrict__ out,
@@ -602,10 +606,10 @@ __global__ __launch_bounds__(256) void linear_head_sgd_kernel(const float* __res
             for (int c = 0; c < n_way; ++c) mx = fmaxf(mx, sl[r * 16 + c]);
             float se = 0.f;
             for (int c = 0; c < n_way; ++c) se += __expf(sl[r * 16 + c] - mx);
-            const float lse = mx + __logf(se);
+            const float lg = __logf(se);
             const int yy = yg[ig[t * bs + r]];
             const float inv = 1.f / (float)k;
-            for (int c = 0; c < n_way; ++c) sl[r * 16 + c] = (__expf(sl[r * 16 + c] - lse) - (c == yy ? 1.f : 0.f)) * inv;
+            for (int c = 0; c < n_way; ++c) sl[r * 16 + c] = (__expf((sl[r * 16 + c] - mx) - lg) - (c == yy ? 1.f : 0.f)) * inv;
         }
         __syncthreads();
         float step_size = lr, inv_sqrt_bc2 = 1.f;
