@@ -21,8 +21,21 @@
 //     ENTRY  C1: BatchNorm1 statistics + affine + ReLU -> r1                      (backbone.py:252-254)
 //     EXIT   C2: BatchNorm2 + BatchNorm(shortcut) + add + ReLU + global average pool   (backbone.py:255-261, :438 AvgPool2d)
 // The gradient and (w, m, v) are bit-identical to wgrad_adam_rows_kernel (same reduction order, same Adam expressions).
-// All request streams are one tile deep: im2col rows, then w/m/v, then next-step activation rows of tile k+1 are requested
-// while tile k is being multiplied (the load counter is in order, so the reduction never waits for the big w/m/v requests).
+//
+// Request streams (what the compiled walk does; listing: profiles/r08_walker_wait_structure.txt).  Per tile and wave, in issue
+// order: 6 im2col rows of tile k+1 (after the reduction's matrix instructions), 12 nontemporal stores of tile k's m, v, w (Adam),
+// 6 next-step activation rows of tile k+1 (after the forward's matrix instructions), 12 nontemporal loads of tile k+2's m, v, w
+// into the register set Adam has just emptied.  The memory counter is in order, and a wait names how many younger requests may
+// stay in flight.  The walk waits in two places only: vmcnt(35..30) ahead of the six LDS stores of the im2col rows (everything
+// requested after those rows stays in flight) and vmcnt(35..30) ahead of the forward's matrix instructions (the same, for the
+// activation rows).  Adam itself never waits: its w/m/v were requested two tiles earlier.  Nothing waits for a request that
+// was issued a few instructions before, and no wait drains the queue.  Three things make that hold:
+//   * every operand request is a buffer load, and a request that must give zeros (padding tap, row beyond the episode) or
+//     nothing (tile after the last) is given an offset past the end of its buffer: the hardware range check returns zeros, so
+//     there is no select after a load and no branch or predicated block around one;
+//   * every request stream is issued on every path, so the compiler counts the same requests between a load and its use
+//     whichever way it looks at the loop;
+//   * the loop holds only steady-state pairs of tiles (tile 0 and an unpaired last tile run outside it).
 #include "mft_common.h"
 #include <math.h>
 
@@ -56,6 +69,8 @@ struct WfArgs {
 };
 
 enum { WF_RAW = 0, WF_ENTRY = 1, WF_EXIT = 2 };
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float lane8_sum(float v) {       // sum over the 8 lanes that share tid >> 3
     v += __shfl_xor(v, 1, 64);
@@ -106,9 +121,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (m < rows) v = *(const f32x4*)(p.dy + (row0 + m) * p.ldy + co0 + acol);
         if (m < 48) *(f32x4*)(As + m * BM + acol) = v;
     }
-    // pixel geometry, packed (image << 16 | (ih0 + 64) << 8 | (iw0 + 64)); -1 = row beyond the episode's pixels
+    // pixel geometry, packed (image << 16 | (ih0 + 64) << 8 | (iw0 + 64)).  A row beyond the episode's pixels gets ih0 = 191: with any
+    // tap it stays at or beyond H (<= 100), so such a row fails the same in-image test as a padding tap and needs no test of its own
     auto geom = [&](int m) {
-        if (m >= rows) return -1;
+        if (m >= rows) return (255 << 8) | 255;
         const int img = (m * p.inv_ohw) >> 16, rem = m - img * ohw;
         const int oh = (rem * p.inv_ow) >> 16, ow = rem - oh * p.OW;
         return (img << 16) | ((oh * p.stride - p.pad + 64) << 8) | (ow * p.stride - p.pad + 64);
@@ -118,14 +134,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int j = 0; j < 6; ++j) bgeo[j] = geom(brow + 8 * j);
 #pragma unroll
     for (int nb = 0; nb < 3; ++nb) xgeo[nb] = geom(nb * 16 + fm);
-    // element offset of the tap's input pixel inside the episode (always a valid address) and whether the tap is inside the image:
-    // the loads are unconditional (a clamped address, then a select) -- no branch per load
-    auto pix_off = [&](int geo, int kh, int kw, bool& ok) -> int {
-        const int img = (geo >> 16) & 255, ih = ((geo >> 8) & 255) - 64 + kh, iw = (geo & 255) - 64 + kw;
-        ok = geo >= 0 && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
-        return ok ? ((img * p.H + ih) * p.W + iw) * p.ldi : 0;
+    // Every operand request of the walk is a buffer load whose hardware range check stands in for a branch or a select: a request
+    // that must deliver zeros (a tap outside the image, a row beyond the episode) or nothing at all (the tile after the last one)
+    // gets the lane offset OOB, which lies past the end of every buffer the launcher accepts, and comes back as zeros without a
+    // memory access.  So nothing touches a loaded register before the instruction that needs it, and all request streams are
+    // issued unconditionally: on every path through the walk the same number of requests lies between a request and its first
+    // use, which is what lets the compiler's wait for it leave all younger requests in flight.
+    constexpr unsigned OOB = 0x80000000u;
+    auto req_off = [&](unsigned off, unsigned drop) -> unsigned {       // drop: 0 or OOB;  exactly OOB when dropped, so that
+        const unsigned o = off | drop;                                  // offsets added later (by code or instruction) cannot wrap
+        return o < OOB ? o : OOB;
+    };
+    // byte offset of the tap's input pixel inside the episode's activation buffer (meaningless when drop is set): no branch, no
+    // predicated block -- two unsigned comparisons combined bitwise
+    auto pix_off = [&](int geo, int kh, int kw, unsigned& drop) -> unsigned {
+        const int img = geo >> 16, ih = ((geo >> 8) & 255) - 64 + kh, iw = (geo & 255) - 64 + kw;
+        const bool ok = ((unsigned)ih < (unsigned)p.H) & ((unsigned)iw < (unsigned)p.W);
+        drop = ok ? 0u : OOB;
+        return (unsigned)(((img * p.H + ih) * p.W + iw) * p.ldi) * 4u;
     };
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    // the episode's x_t and x_{t+1}: wave-uniform descriptors that end with the episode's last pixel row (x_{t+1}: empty when there
+    // is no next step, every request through it is then dropped)
+    const unsigned act_bytes = (unsigned)((p.ipg * p.H * p.W - 1) * p.ldi + p.Cin) * 4u;
+    const size_t act_e = (size_t)(img0 * p.H * p.W) * p.ldi;
+    const __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + act_e), 0, act_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xn_rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((fwd ? p.xn : p.in) + act_e), 0, fwd ? act_bytes : 0u, 0x00020000);
+    auto load16 = [&](__amdgpu_buffer_rsrc_t rs, unsigned byte_off) -> f32x4 {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0));
+    };
+    auto load16_nt = [&](__amdgpu_buffer_rsrc_t rs, unsigned byte_off) -> f32x4 {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 2));      // 2 = nontemporal
+    };
 
     // (tap, input-channel tile) of the tile the NEXT operand requests are for, carried incrementally (no division per tile)
     int nkh = 0, nkw = 0, nci0 = 0;
@@ -137,55 +178,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     f32x4 vb[6];
-    const float* const in_e = p.in + (img0 * p.H * p.W) * p.ldi;            // wave-uniform bases; 32-bit lane offsets
-    auto load_b = [&](int kh, int kw, int ci0) {
+    auto load_b = [&](int kh, int kw, int ci0, unsigned drop_all) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            bool ok;
-            const int o = pix_off(bgeo[j], kh, kw, ok);
-            const f32x4 v = *(const f32x4*)(in_e + (o + ci0 + bcol));
-            vb[j] = ok ? v : zero4;
+            unsigned drop;
+            const unsigned o = pix_off(bgeo[j], kh, kw, drop);
+            vb[j] = load16(in_rs, req_off(o + 4u * (unsigned)(ci0 + bcol), drop | drop_all));
         }
     };
     f32x4 xb[3][2];
-    const float* const xn_e = p.xn + (img0 * p.H * p.W) * p.ldi;
-    auto load_x = [&](int kh, int kw, int ci0) {
-        const int xo = ci0 + 32 * wave + 4 * fq;
+    auto load_x = [&](int kh, int kw, int ci0, unsigned drop_all) {
+        const unsigned xo = 4u * (unsigned)(ci0 + 32 * wave + 4 * fq);
 #pragma unroll
         for (int nb = 0; nb < 3; ++nb) {
-            bool ok;
-            const int o = pix_off(xgeo[nb], kh, kw, ok);
+            unsigned drop;
+            const unsigned o = req_off(pix_off(xgeo[nb], kh, kw, drop) + xo, drop | drop_all);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const f32x4 v = *(const f32x4*)(xn_e + (o + xo + 16 * j));
-                xb[nb][j] = ok ? v : zero4;
-            }
+            for (int j = 0; j < 2; ++j) xb[nb][j] = load16(xn_rs, o + 64u * j);
         }
     };
-    // this workgroup's 32 rows of w / m / v: wave-uniform 64-bit bases, 32-bit lane offsets (a row block is < 2^31 floats)
+    // this workgroup's 32 rows of w / m / v: wave-uniform descriptors of exactly those rows, 32-bit lane offsets (the launcher
+    // keeps a row block below 2^31 bytes)
     const int q = tid & 31, rr = tid >> 5;
     const long long tile_base = (long long)g * p.dwgs + (long long)co0 * p.Kpad;
-    float* const wg_ = p.w + tile_base;
-    float* const mg_ = p.m + tile_base;
-    float* const vg_ = p.v + tile_base;
+    const unsigned wmv_bytes = (unsigned)(BM * p.Kpad) * 4u;
+    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + tile_base), 0, wmv_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t m_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.m + tile_base), 0, wmv_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.v + tile_base), 0, wmv_bytes, 0x00020000);
     const int lo0 = rr * p.Kpad + 4 * q;
+    const unsigned row8 = 4u * (unsigned)(8 * p.Kpad);          // bytes between a lane's four rows
     // two register sets: while Adam consumes tile k from one, tile k+1 sits (landed or landing) in the other and tile k+2 is
     // requested into the first as soon as Adam is done with it
     f32x4 am[4], av[4], aw[4], bm[4], bv[4], bw[4];
-    auto load_wmv = [&](int kt, f32x4 (&M)[4], f32x4 (&V)[4], f32x4 (&W)[4]) {
+    auto load_wmv = [&](int kt, f32x4 (&M)[4], f32x4 (&V)[4], f32x4 (&W)[4], unsigned drop_all) {
+        const unsigned o = req_off(4u * (unsigned)(lo0 + kt * BN), drop_all);       // K index of tile kt = kt * 128 (tap-major)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int gi = lo0 + 8 * u * p.Kpad + kt * BN;       // K index of tile kt = kt * 128 (tap-major)
-            M[u] = __builtin_nontemporal_load((const f32x4*)(mg_ + gi));
-            V[u] = __builtin_nontemporal_load((const f32x4*)(vg_ + gi));
-            W[u] = __builtin_nontemporal_load((const f32x4*)(wg_ + gi));
+            M[u] = load16_nt(m_rs, o + u * row8);
+            V[u] = load16_nt(v_rs, o + u * row8);
+            W[u] = load16_nt(w_rs, o + u * row8);
         }
     };
     // request order = order of need (the load counter is in order): operand rows of tile 0, of tile 1, w/m/v of tiles 0 and 1
-    load_b(0, 0, 0);
-    if (fwd) load_x(0, 0, 0);
-    load_wmv(0, am, av, aw);
-    if (n_kt > 1) load_wmv(1, bm, bv, bw);
+    load_b(0, 0, 0, 0u);
+    load_x(0, 0, 0, 0u);
+    load_wmv(0, am, av, aw, 0u);
+    load_wmv(1, bm, bv, bw, n_kt > 1 ? 0u : OOB);
     advance();                            // (nkh, nkw, nci0) = tile 1
     f32x4 accf[3][2];
 #pragma unroll
@@ -196,7 +234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float inv_sqrt_bc2 = p.hyper ? p.hyper[1] : p.inv_sqrt_bc2;
 
     auto tile = [&](int kt, f32x4 (&cm)[4], f32x4 (&cv)[4], f32x4 (&cw)[4]) {
-        const bool more = kt + 1 < n_kt;
+        const unsigned last = kt + 1 < n_kt ? 0u : OOB;          // OOB: there is no next tile, its operand requests are dropped
         // ---- gradient tile: G[co][k] = sum_rows dY[row][co] * im2col[row][k]
 #pragma unroll
         for (int j = 0; j < 6; ++j) *(f32x4*)(Bs + (brow + 8 * j) * BLD + bcol) = vb[j];
@@ -213,7 +251,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int t = 0; t < 8; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * t * BM], bp[2 * t * BLD], acc, 0, 0, 0);
         }
-        if (more) load_b(nkh, nkw, nci0);             // next tile's im2col rows (L2) under the epilogue
+        load_b(nkh, nkw, nci0, last);                 // next tile's im2col rows (L2) under the epilogue
 #pragma unroll
         for (int e = 0; e < 16; ++e) Gs[((e & 3) + 8 * (e >> 2) + 4 * h) * GLD + wave * 32 + r] = acc[e];
         __syncthreads();
@@ -221,13 +259,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int gi = lo0 + 8 * u * p.Kpad + kt * BN;
+            const int go = 4 * gi;
             float* gcell = Gs + (rr + 8 * u) * GLD + 4 * q;
             const f32x4 ge = *(const f32x4*)gcell;
             if (FAST) mft_adam4_fast(cm[u], cv[u], cw[u], ge, p.b1, p.b2, p.eps, step_size, inv_sqrt_bc2);
             else mft_adam4_exact(cm[u], cv[u], cw[u], ge, p.b1, p.b2, p.eps, step_size, inv_sqrt_bc2);
-            __builtin_nontemporal_store(cm[u], (f32x4*)(mg_ + gi));
-            __builtin_nontemporal_store(cv[u], (f32x4*)(vg_ + gi));
-            __builtin_nontemporal_store(cw[u], (f32x4*)(wg_ + gi));
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cm[u]), m_rs, go, 0, 2);      // 2 = nontemporal
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cv[u]), v_rs, go, 0, 2);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cw[u]), w_rs, go, 0, 2);
             if (p.dw) *(f32x4*)(p.dw + tile_base + gi) = ge;
             if (fwd) *(f32x4*)gcell = cw[u];
         }
@@ -246,18 +285,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         accf[nb][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i], xb[nb][j][i], accf[nb][1], 0, 0, 0);
                     }
             }
-            if (more) load_x(nkh, nkw, nci0);
         }
+        load_x(nkh, nkw, nci0, last);
         // tile k+2's w/m/v into the set Adam has just finished with: requested AFTER everything tile k+1 needs first
-        if (kt + 2 < n_kt) load_wmv(kt + 2, cm, cv, cw);
+        load_wmv(kt + 2, cm, cv, cw, kt + 2 < n_kt ? 0u : OOB);
         advance();
         // (the next tile's first barrier separates these fragment reads of Gs from its next overwrite)
     };
-    for (int kt = 0; kt < n_kt; kt += 2) {
-        tile(kt, am, av, aw);
-        if (kt + 1 < n_kt) tile(kt + 1, bm, bv, bw);
+    // The compiler sizes every wait in the loop for the path with the fewest requests between a request and its use, over all
+    // paths it can see.  So the loop is kept to the steady state: tile 0, whose operands the requests above fetched in another
+    // order, runs ahead of it; tiles go in pairs (one per register set) with no way out between the two -- with an exit there the
+    // compiled loop also has a path from one half straight back to itself, on which that half's w/m/v requests lie only a few
+    // requests before Adam -- and an unpaired last tile runs after the loop.
+    tile(0, am, av, aw);
+    int kt = 1;
+    for (; kt + 1 < n_kt; kt += 2) {
+        tile(kt, bm, bv, bw);
+        tile(kt + 1, am, av, aw);
     }
+    if (kt < n_kt) tile(kt, bm, bv, bw);
     if (!fwd) return;
+
+    // The epilogue's arguments (up to 13 pointers) are read from the kernel-argument segment only here.  Fetched with the others at
+    // the kernel's entry they stay in scalar registers for the whole walk, and the EXIT form then runs out of them.
+    const WfArgs __attribute__((address_space(4)))* e =
+        (const WfArgs __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(e));                       // opaque: the loads through `e` cannot move above this point
+    struct {                                          // (rows again: no row mask of the walk's set-up is kept alive for the write-out)
+        int rows, Cout, hw; long long gbs; float bn_eps;
+        float *raw, *act, *mean, *rstd, *means, *rstds, *pooled;
+        const float *gamma, *beta, *sc, *gs, *bs;
+    } const t = {e->rows, e->Cout, e->hw, e->gbs, e->bn_eps, e->raw, e->act, e->mean, e->rstd, e->means, e->rstds, e->pooled,
+                 e->gamma, e->beta, e->sc, e->gs, e->bs};
 
     // ---- the four k-slices' partial outputs, summed in fixed order
     __syncthreads();
@@ -295,15 +354,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const float d = x[i] - mu;
                     s += d * d;
                 }
-            rs = 1.0f / sqrtf(lane8_sum(s) * inv_rows + p.bn_eps);
+            rs = 1.0f / sqrtf(lane8_sum(s) * inv_rows + t.bn_eps);
         };
         const int co = co0 + c;
         float mu, rs;
         stats(val, mu, rs);
-        const float ga = p.gamma[g * p.gbs + co], be = p.beta[g * p.gbs + co];
+        const float ga = t.gamma[g * t.gbs + co], be = t.beta[g * t.gbs + co];
         if (pl == 0) {
-            p.mean[(long long)g * p.Cout + co] = mu;
-            p.rstd[(long long)g * p.Cout + co] = rs;
+            t.mean[(long long)g * t.Cout + co] = mu;
+            t.rstd[(long long)g * t.Cout + co] = rs;
         }
         if (MODE == WF_ENTRY) {
 #pragma unroll
@@ -316,14 +375,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const int px = pl + 8 * i;
-                sv[i] = px < rows ? p.sc[(row0 + px) * p.Cout + co] : 0.f;
+                sv[i] = px < rows ? t.sc[(row0 + px) * t.Cout + co] : 0.f;
             }
             float mus, rss;
             stats(sv, mus, rss);
-            const float gas = p.gs[g * p.gbs + co], bes = p.bs[g * p.gbs + co];
+            const float gas = t.gs[g * t.gbs + co], bes = t.bs[g * t.gbs + co];
             if (pl == 0) {
-                p.means[(long long)g * p.Cout + co] = mus;
-                p.rstds[(long long)g * p.Cout + co] = rss;
+                t.means[(long long)g * t.Cout + co] = mus;
+                t.rstds[(long long)g * t.Cout + co] = rss;
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -340,17 +399,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         const int px = p2 + 8 * i;
-        if (px < rows) {
-            p.raw[(row0 + px) * p.Cout + co0 + c2] = T0[px * TLD + c2];
-            if (MODE != WF_RAW) p.act[(row0 + px) * p.Cout + co0 + c2] = T1[px * TLD + c2];
+        if (px < t.rows) {
+            t.raw[(row0 + px) * t.Cout + co0 + c2] = T0[px * TLD + c2];
+            if (MODE != WF_RAW) t.act[(row0 + px) * t.Cout + co0 + c2] = T1[px * TLD + c2];
         }
     }
     if (MODE == WF_EXIT) {
-        const int n_img = rows / p.hw;
+        const int n_img = t.rows / t.hw;
         if (p2 < n_img) {                              // global average pool of the block output (<= 8 images per episode)
             float sum = 0.f;
-            for (int k2 = 0; k2 < p.hw; ++k2) sum += T1[(p2 * p.hw + k2) * TLD + c2];
-            p.pooled[((long long)g * n_img + p2) * p.Cout + co0 + c2] = sum * (1.f / (float)p.hw);
+            for (int k2 = 0; k2 < t.hw; ++k2) sum += T1[(p2 * t.hw + k2) * TLD + c2];
+            t.pooled[((long long)g * n_img + p2) * t.Cout + co0 + c2] = sum * (1.f / (float)t.hw);
         }
     }
 }
@@ -377,6 +436,8 @@ extern "C" int mft_wgrad_adam_next_forward(const float* x, int ldx, const float*
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
     const int rows = imgs_per_group * OH * OW;
     if (rows > 48 || OH < 1 || OW < 1 || H > 100 || W > 100 || imgs_per_group > 8) return MFT_EINVAL;
+    // the kernel addresses an episode's activations and a workgroup's 32 weight rows with 32-bit byte offsets below 2^31
+    if ((long long)imgs_per_group * H * W * ldx * 4 >= (1LL << 31) || 32LL * KH * KW * Cin * 4 >= (1LL << 31)) return MFT_EINVAL;
     if (mode < WF_RAW || mode > WF_EXIT) return MFT_EINVAL;
     if (x_next != nullptr) {
         if (raw == nullptr) return MFT_EINVAL;
