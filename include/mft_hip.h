@@ -836,6 +836,15 @@ typedef struct MftFwtGradJob {
 } MftFwtGradJob;
 int mft_fwt_unfold(const MftFwtGradJob* jobs, int n_layers, int groups, int ld, const float* noise, void* stream);
 
+/* Episodic evaluation on frozen features (csrc/feature_eval.hip) ------------------------------------- */
+/* Top-1 count per episode of a lockstep batch (MetaTemplate.correct, meta_template.py:62-67, for n_episodes at once): scores
+ * [n_episodes * n_way * n_query, ld], row r of an episode has label r / n_query.  pred (nullable, one int per row) = the LOWEST
+ * column index attaining the row maximum over columns 0 .. n_way-1, a NaN comparing greater than every number (the first NaN
+ * wins: numpy's and torch's argmax); columns n_way .. ld-1 are never read.  correct[e] = rows of episode e whose prediction
+ * equals their label.  One workgroup per episode, integer sums in a fixed tree, no atomics: two runs give the same bytes.
+ * MFT_EINVAL outside n_way 1..64, ld >= n_way, n_query >= 1, n_episodes >= 1. */
+int mft_episode_top1(const float* scores, int ld, int n_episodes, int n_way, int n_query, int* correct, int* pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

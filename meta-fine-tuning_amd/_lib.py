@@ -171,6 +171,7 @@ SIGNATURES = {
     "mft_gather_query_scores_backward": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "mft_fwt_draw_fold": [_P, _I, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _P, _P],
     "mft_fwt_unfold": [_P, _I, _I, _I, _P, _P],
+    "mft_episode_top1": [_P, _I, _I, _I, _I, _P, _P, _P],
 }
 # test / A-B hooks (include/mft_hip_testing.h): form selection for tests/ and tools/, never called by the product path
 TESTING_SIGNATURES = {

@@ -267,6 +267,42 @@ def linear_head_adapt(z_support, y_support, z_query, w, b, n_way, n_support, epo
     return ops.gemm(z_query, K, wpad[:n_way].contiguous(), n_way, bias=bias[0].contiguous())
 
 
+ADAPT_MAX_WAY = 16          # mft_linear_head_sgd_run / mft_dist_head_sgd_run: n_way 1..16, mini-batches of at most 16 rows
+
+
+def linear_head_adapt_episodes(z_support, y_support, z_query, w0, b0, n_way, n_support, epochs=100, batch_size=4, perms=None):
+    """``linear_head_adapt`` for E episodes at once (the `test` driver): z_support [E, S, D], y_support [S]
+    or [E, S], z_query [E, Q, D], w0 [E, n_way, D], b0 [E, n_way] (not modified).  The permutations of all epochs are drawn
+    first, episode by episode (``perms[e][epoch]`` pins them: the `test` driver draws them itself, interleaved with its episode
+    draws in the sequential order), as ``dist_head_adapt`` does.  ONE mft_linear_head_sgd_run launch trains the E heads (a
+    workgroup per episode, the arithmetic of the one-episode launch), ONE grouped GEMM scores every episode's queries with its own
+    head; the grouped launcher takes a shared bias only, so the per-episode bias is added to its output -- the single rounding
+    the one-episode GEMM's epilogue makes.  -> raw scores [E * Q, n_way]."""
+    dev = z_support.device
+    E, S, D = z_support.shape
+    Q = z_query.shape[1]
+    if S != n_way * n_support or D % 32 != 0:
+        raise ValueError("linear_head_adapt_episodes: %d support rows of %d features are not n_way * n_support = %d rows of a multiple "
+                         "of 32 features" % (S, D, n_way * n_support))
+    if not 1 <= int(n_way) <= ADAPT_MAX_WAY or not 1 <= int(batch_size) <= 16 or epochs < 1:
+        raise ValueError("linear-head adaptation: n_way = %d, batch_size = %d, epochs = %d are not supported (1 <= n_way <= %d, "
+                         "1 <= batch_size <= 16, epochs >= 1)" % (int(n_way), int(batch_size), epochs, ADAPT_MAX_WAY))
+    tables = np.stack([adaptation_table(S, epochs, batch_size, None if perms is None else perms[e]) for e in range(E)])
+    y = np.broadcast_to(np.asarray(y_support).astype(np.int32).reshape(-1, S), (E, S)).copy()
+    table = torch.from_numpy(tables).to(dev)
+    y_dev = torch.from_numpy(y).to(dev)
+    W = w0.detach().to(dev, torch.float32).reshape(E, n_way, D).clone()
+    bias = b0.detach().to(dev, torch.float32).reshape(E, n_way).clone()
+    rc = ops._lib.lib().mft_linear_head_sgd_run(ops._p(z_support.contiguous().float()), ops._p(y_dev), ops._p(table), E, S, D, n_way,
+                                                table.shape[1], table.shape[2], ops._p(W), ops._p(bias), 0.01, 0.9, 0.9, 0.001,
+                                                ops._stream())
+    ops._lib.check(rc, "mft_linear_head_sgd_run")
+    zq = z_query.contiguous().float().view(E * Q, D)
+    scores = ops.gemm(zq, D, W if E > 1 else W[0], n_way, rows_per_group=Q if E > 1 else 0)
+    scores.view(E, Q, n_way).add_(bias.view(E, 1, n_way))
+    return scores
+
+
 def adaptation_table(support_size, epochs, batch_size, perms=None):
     """Index table [epochs * ceil(support_size / batch_size), batch_size] of the head-adaptation loop (baselinefinetune.py:42-46):
     one permutation of the support rows per epoch -- drawn from the global numpy stream unless ``perms`` gives them -- cut into

@@ -1048,6 +1048,26 @@ def gather_rows(src2d, idx_i32, out=None):
     return out
 
 
+TOP1_MAX_WAY = 64
+
+
+def episode_top1(scores, n_episodes, n_way, n_query, need_pred=False):
+    """Top-1 count of every episode of a lockstep batch (csrc/feature_eval.hip): scores [n_episodes * n_way * n_query, ld >= n_way]
+    float32 with unit column stride, row r of an episode labelled r // n_query -> correct [n_episodes] int32, and with
+    ``need_pred`` also the predictions [rows] int32 (first index of the row maximum over the first n_way columns)."""
+    _dist_rows(scores, "episode_top1")
+    rows = n_episodes * n_way * n_query
+    if not 1 <= int(n_way) <= TOP1_MAX_WAY or n_query < 1 or n_episodes < 1 or scores.shape[0] != rows or scores.shape[1] < n_way \
+            or scores.stride(0) < scores.shape[1]:
+        raise ValueError("episode_top1: scores %s (row stride %d) are not [%d episodes * %d way * %d query, >= n_way] with "
+                         "1 <= n_way <= %d" % (tuple(scores.shape), scores.stride(0), n_episodes, n_way, n_query, TOP1_MAX_WAY))
+    correct = torch.empty((n_episodes,), device=scores.device, dtype=torch.int32)
+    pred = torch.empty((rows,), device=scores.device, dtype=torch.int32) if need_pred else None
+    _lib.check(_lib.lib().mft_episode_top1(_p(scores), scores.stride(0), n_episodes, n_way, n_query, _p(correct), _p(pred),
+                                           _stream()), "mft_episode_top1")
+    return (correct, pred) if need_pred else correct
+
+
 # ---------------------------------------------------------------------------------------------- MatchingNet head (csrc/matchingnet.hip)
 MN_D, MN_MAX_S, MN_MAX_WAY = 512, 256, 32
 MN_KEYS = ("FCE.lstmcell.weight_ih", "FCE.lstmcell.weight_hh", "FCE.lstmcell.bias_ih", "FCE.lstmcell.bias_hh",
