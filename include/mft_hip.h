@@ -532,6 +532,28 @@ int mft_ridge_backward_support(const float* feats, int ld, int episodes, int n_w
                                const float* L, const float* alpha, const float* W, const float* dW, const double* dscale_part,
                                float* dfeats, int ldd, float* dscale, void* stream);
 
+/* MetaOptNet multi-class SVM head (csrc/svm.hip): the Crammer-Singer dual
+ *   alpha = argmin 1/2 tr(alpha^T M alpha) - tr(Y^T alpha)  s.t.  alpha <= C Y,  alpha 1 = 0      M = Z_S Z_S^T + I,  C = 0.1
+ * of every episode per launch; layout and domain of the ridge head above.  scores, dZ_Q, dW and the dscale shares come from
+ * mft_ridge_scores / mft_ridge_backward_query on this head's W.
+ *   gram:   M [episodes, S, S] in float64, both triangles.
+ *   solve:  one workgroup per episode, every iterate in double (work [episodes, 16384] float64: workspace; work[e][0] returns the products used); alpha [episodes, S, n_way] (fp32, never above C Y);
+ *           free_mask [episodes, S, n_way] (1 where alpha < C Y in the double iterate); W [episodes, n_way, D] = (Z_S^T alpha)^T
+ *           from the stored alpha; status [episodes] = 0 when the optimality test passed, 1 when the episode used
+ *           MFT_SVM_MAX_PRODUCTS products of M with an [S, n_way] matrix (alpha is then the last iterate) or M is not finite
+ *           (alpha and W are then NaN).
+ *   backward_support: A = Z_S dW^T; U [S, n_way] with U = 0 off the free set, U 1 = 0, (M U + w 1^T) = A on it (conjugate
+ *           gradients, at most MFT_SVM_MAX_PRODUCTS products); dfeats support rows = alpha dW - U W - alpha (Z_S^T U)^T;
+ *           dscale[0] = the sum of dscale_part in index order.
+ * Fixed summation order, no atomics.  MFT_EINVAL as for the ridge head. */
+#define MFT_SVM_MAX_PRODUCTS 65536
+int mft_svm_gram(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, double* M, void* stream);
+int mft_svm_solve(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const double* M,
+                  double* work, float* alpha, unsigned char* free_mask, float* W, int* status, void* stream);
+int mft_svm_backward_support(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D,
+                             const double* M, const float* alpha, const unsigned char* free_mask, const float* W,
+                             const float* dW, const double* dscale_part, float* dfeats, int ldd, float* dscale, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

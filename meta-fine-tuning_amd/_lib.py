@@ -97,6 +97,9 @@ SIGNATURES = {
     "mft_ridge_scores": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     "mft_ridge_backward_query": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
     "mft_ridge_backward_support": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "mft_svm_gram": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "mft_svm_solve": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "mft_svm_backward_support": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "mft_dist_linear_forward": [_P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P],
     "mft_dist_linear_backward": [_P, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _P],
     "mft_dist_head_sgd_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P],

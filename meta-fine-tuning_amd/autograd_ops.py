@@ -545,6 +545,52 @@ def metaoptnet_head(feats, scale, n_way, n_support, n_query, episodes=1):
     return ops.ridge_forward(feats.detach(), scale.detach(), episodes, n_way, n_support, n_query)[0]
 
 
+class _SvmHeadFn(torch.autograd.Function):
+    """MetaOptNet SVM head with a hand-written backward: ops.svm_forward keeps alpha, the free mask and W,
+    ops.svm_backward solves the adjoint system on that mask and returns the gradients of every feature row and of ``scale``."""
+
+    @staticmethod
+    def forward(ctx, feats, scale, n_way, n_support, n_query, episodes):
+        scores, tape = ops.svm_forward(feats, scale.detach(), episodes, n_way, n_support, n_query, save=True)
+        ctx.save_for_backward(feats, scale, tape["alpha"], tape["free"], tape["W"])
+        ctx.shape = tape["shape"]
+        _SVM_STATUS[0] = tape["status"]
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, scale, alpha, free, W = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.stride(1) == 1) else dscores.contiguous().float()
+        dfeats, dscale = ops.svm_backward(dict(feats=feats, scale=scale.detach(), alpha=alpha, free=free, W=W, shape=ctx.shape), d)
+        return (dfeats if ctx.needs_input_grad[0] else None, dscale.view(scale.shape) if ctx.needs_input_grad[1] else None,
+                None, None, None, None)
+
+
+_SVM_STATUS = [None]
+
+
+def metaoptnet_svm_status():
+    """``status`` [episodes] int32 of the last metaoptnet_svm_head call (0 = the solve's optimality test passed), still on the
+    device: reading it is the caller's host sync, none is made here.  None before the first call."""
+    return _SVM_STATUS[0]
+
+
+def metaoptnet_svm_head(feats, scale, n_way, n_support, n_query, episodes=1):
+    """MetaOptNet(head="svm").set_forward tail: as metaoptnet_head, with W from the Crammer-Singer dual of
+    the support rows in the place of the ridge regression.  Differentiable (features and scale) when autograd records; the
+    no-grad path saves nothing.  metaoptnet_svm_status() returns the call's status tensor."""
+    _require_cuda(feats, "MetaOptNet head")
+    _require_cuda(scale, "MetaOptNet head")
+    ops.svm_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and (feats.requires_grad or scale.requires_grad):
+        return _SvmHeadFn.apply(feats, scale, n_way, n_support, n_query, episodes)
+    scores, tape = ops.svm_forward(feats.detach(), scale.detach(), episodes, n_way, n_support, n_query)
+    _SVM_STATUS[0] = tape["status"]
+    return scores
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

@@ -296,8 +296,10 @@ class FinetuneEngine:
         ``head_state`` holds the twelve FCE.lstmcell.* / G_encoder.* tensors (ops.MN_KEYS).
         "ridge": finetune.finetune with a MetaOptNet model -- the inner loop of "gnn" unchanged, scores = the ridge-regression head
         (ops.ridge_forward with its softmax epilogue, all E episodes per launch) on the final-pass features; ``head_state`` holds
-        ``scale``."""
-        assert mode in ("gnn", "linear", "proto", "dist", "matching", "ridge")
+        ``scale``.
+        "svm": as "ridge" with the SVM head of MetaOptNet(head="svm") (ops.svm_forward: float64 Gram matrix, dual solve,
+        mft_ridge_scores with its softmax epilogue, all E episodes per launch); ``svm_status`` keeps the last solve's status."""
+        assert mode in ("gnn", "linear", "proto", "dist", "matching", "ridge", "svm")
         refuse_feature_wise(state, "FinetuneEngine")
         self.mode = mode
         self.views = mode not in ("linear", "dist")      # the inner loop trains on every view (finetune()); "linear" / "dist" on view 0 only
@@ -360,7 +362,7 @@ class FinetuneEngine:
             ops.mn_check(self.E, n_way, n_support, n_query)
             src = head_state if head_state is not None else state
             self.MN = {k: src[k].detach().to(self.dev, torch.float32).contiguous().clone() for k in ops.MN_KEYS}
-        if mode == "ridge":
+        if mode in ("ridge", "svm"):
             ops.ridge_check(self.E, n_way, n_support, n_query)
             src = head_state if head_state is not None else state
             self.ridge_scale = src["scale"].detach().to(self.dev, torch.float32).reshape(1).clone()
@@ -750,6 +752,10 @@ class FinetuneEngine:
             return ops.softmax_rows(logp).view(self.E, self.n_way * self.n_query, self.n_way), feats
         if self.mode == "ridge":
             sc, _ = ops.ridge_forward(feats, self.ridge_scale, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
+            return sc.view(self.E, self.n_way * self.n_query, self.n_way), feats
+        if self.mode == "svm":
+            sc, tape = ops.svm_forward(feats, self.ridge_scale, self.E, self.n_way, self.n_support, self.n_query, softmax=True)
+            self.svm_status = tape["status"]
             return sc.view(self.E, self.n_way * self.n_query, self.n_way), feats
         ns = self.n_support // 2 if self.fold50 else self.n_support
         scores = Fn.gnnnet_scores(self.G, feats, self.E, self.n_way, ns, self.n_query, arena, fold=self.fold50)

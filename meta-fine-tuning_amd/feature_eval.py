@@ -181,9 +181,12 @@ def accuracy_line(acc_all):
     return '%d Test Acc = %4.2f%% +- %4.2f%%' % (iter_num, np.mean(acc_all), 1.96 * np.std(acc_all) / np.sqrt(iter_num))
 
 
-def build_model(method, model_func, n_way, n_support):
-    """The model `test` scores with: BaselineFinetune for the two baselines, GnnNet, or the method's class of train.HEAD_METHODS."""
+def build_model(method, model_func, n_way, n_support, head="ridge"):
+    """The model `test` scores with: BaselineFinetune for the two baselines, GnnNet, or the method's class of train.HEAD_METHODS
+    (``head``: MetaOptNet's, --head)."""
+    from .io_utils import method_dir_name
     from .train import HEAD_METHODS
+    method_dir_name(method, head)                         # a head that is unknown or not this method's is a ValueError
     if method == 'baseline':
         return BaselineFinetune(model_func, n_way, n_support)
     if method == 'baseline++':
@@ -191,6 +194,7 @@ def build_model(method, model_func, n_way, n_support):
     if method == 'gnnnet':
         return GnnNet(model_func, n_way=n_way, n_support=n_support)
     if method in HEAD_METHODS:
-        return HEAD_METHODS[method](model_func, n_way=n_way, n_support=n_support)
+        kw = dict(head=head) if method == 'metaoptnet' else {}
+        return HEAD_METHODS[method](model_func, n_way=n_way, n_support=n_support, **kw)
     raise NotImplementedError("--method %s: 'baseline', 'baseline++', 'gnnnet', %s are on the HIP path"
                               % (method, ", ".join(repr(m) for m in sorted(HEAD_METHODS))))

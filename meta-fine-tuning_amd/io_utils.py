@@ -10,6 +10,19 @@ from . import backbone
 
 model_dict = dict(ResNet10=backbone.ResNet10, ResNet10_FW=backbone.ResNet10_FW)      # ResNet18 is off the hot path; ResNet10_FW: DESIGN §15
 
+HEADS = ("ridge", "svm")             # MetaOptNet's heads (DESIGN.md sections 14 and 17)
+
+
+def method_dir_name(method, head="ridge"):
+    """The method's part of a checkpoint / feature directory name: ``metaoptnet_svm`` for the SVM head, the method otherwise (the
+    default head changes no name)."""
+    if head not in HEADS:
+        raise ValueError("--head %r: %s" % (head, " or ".join(HEADS)))
+    if head != "ridge" and method != "metaoptnet":
+        raise ValueError("--head %s belongs to --method metaoptnet, not to --method %s" % (head, method))
+    return method if head == "ridge" else "%s_%s" % (method, head)
+
+
 # (flag, kwargs) for every script
 _COMMON = [
     ("--dataset", dict(default="miniImagenet", help="training base model")),
@@ -17,6 +30,7 @@ _COMMON = [
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
     ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/gnnnet/all")),
+    ("--head", dict(default="ridge", help="--method metaoptnet: its head, ridge (ridge regression) or svm")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),
     ("--test_n_way", dict(default=5, type=int, help="class num to classify for testing (validation)")),
     ("--n_shot", dict(default=5, type=int, help="number of labeled data in each class, same as n_support")),

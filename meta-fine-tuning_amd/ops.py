@@ -1374,3 +1374,72 @@ def ridge_backward(tape, dscores):
                                             _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream()),
                "mft_ridge_backward_support")
     return dfeats, dscale
+
+
+# ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
+SVM_C = 0.1                         # the published C_reg; a constant of the kernels
+SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1
+_SVM_WORK = 1024 * 16               # float64 workspace of mft_svm_solve per episode
+
+svm_check = ridge_check             # the SVM launchers' domain is the ridge head's
+
+
+def _svm_gram(feats, E, n_way, n_support, n_query):
+    S = n_way * n_support
+    M = torch.empty((E, S, S), device=feats.device, dtype=torch.float64)
+    _lib.check(_lib.lib().mft_svm_gram(_p(feats), feats.stride(0), E, n_way, n_support, n_query, RIDGE_D, _p(M), _stream()), "mft_svm_gram")
+    return M
+
+
+def svm_forward(feats, scale, episodes, n_way, n_support, n_query, softmax=False, save=False):
+    """MetaOptNet-SVM head forward: feats and scale as for ridge_forward -> (scores
+    [episodes*n_way*n_query, n_way], tape); ``softmax``: the row softmax of the scores instead.  Three launches whatever the shape:
+    float64 Gram matrix, the dual solve (alpha, free mask, W, status), mft_ridge_scores.  The tape always holds ``status``
+    [episodes] int32 (0 = the optimality test passed) and ``products`` [episodes] (the solve's products M x [S, n_way]), neither
+    read back here; ``save``: also alpha, the free mask and W for svm_backward."""
+    _ridge_feats(feats, episodes, n_way, n_support, n_query)
+    _ridge_scale(scale)
+    E, D, S, Q = episodes, RIDGE_D, n_way * n_support, n_way * n_query
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    alpha, W, scores = new(E, S, n_way), new(E, n_way, D), new(E * Q, n_way)
+    free = torch.empty((E, S, n_way), device=dev, dtype=torch.uint8)
+    status = torch.empty((E,), device=dev, dtype=torch.int32)
+    work = torch.empty((E, _SVM_WORK), device=dev, dtype=torch.float64)
+    M = _svm_gram(feats, E, n_way, n_support, n_query)
+    h, ld = _lib.lib(), feats.stride(0)
+    _lib.check(h.mft_svm_solve(_p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(work), _p(alpha), _p(free), _p(W), _p(status),
+                               _stream()), "mft_svm_solve")
+    _lib.check(h.mft_ridge_scores(_p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
+                                  _stream()), "mft_ridge_scores")
+    products = work[:, 0]               # float64 [episodes]: products M x [S, n_way] the solve used
+    if not save:
+        return scores, dict(status=status, products=products)
+    return scores, dict(feats=feats, scale=scale, alpha=alpha, free=free, W=W, status=status, products=products,
+                        shape=(E, n_way, n_support, n_query))
+
+
+def svm_backward(tape, dscores):
+    """d(scores) [episodes*n_way*n_query, n_way] -> (dfeats [rows, 512] with every row written, dscale [1]) from svm_forward's
+    tape.  Three launches whatever the shape: the float64 Gram matrix again (it is not kept), mft_ridge_backward_query (dZ_Q, dW,
+    the shares of dscale), the support side (A, the adjoint solve for U on the saved free mask, dZ_S)."""
+    E, n_way, n_support, n_query = tape["shape"]
+    feats, scale = tape["feats"], tape["scale"]
+    D, Q = RIDGE_D, n_way * n_query
+    if not dscores.is_cuda:
+        raise RuntimeError("MetaOptNet head: d(scores) is on %s -- the MI355X path has no CPU fallback" % dscores.device)
+    if dscores.dtype != torch.float32 or dscores.dim() != 2 or dscores.stride(1) != 1:
+        raise RuntimeError("MetaOptNet head: expected float32 d(scores) with unit column stride")
+    if tuple(dscores.shape) != (E * Q, n_way):
+        raise ValueError("svm_backward: dscores is %s, expected [%d, %d]" % (tuple(dscores.shape), E * Q, n_way))
+    new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
+    dfeats, dW, dscale = new(feats.shape[0], D), new(E, n_way, D), new(1)
+    part = torch.empty(E * 8, device=feats.device, dtype=torch.float64)
+    M = _svm_gram(feats, E, n_way, n_support, n_query)
+    h, ld = _lib.lib(), feats.stride(0)
+    _lib.check(h.mft_ridge_backward_query(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
+                                          dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream()), "mft_ridge_backward_query")
+    _lib.check(h.mft_svm_backward_support(_p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(tape["alpha"]), _p(tape["free"]),
+                                          _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream()),
+               "mft_svm_backward_support")
+    return dfeats, dscale

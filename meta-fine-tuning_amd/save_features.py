@@ -12,7 +12,7 @@ import torch
 
 from . import augment, backbone, configs, settings, synthetic
 from .data.feature_loader import save_features_file
-from .io_utils import get_assigned_file, get_best_file, get_resume_file, model_dict, parse_args
+from .io_utils import get_assigned_file, get_best_file, get_resume_file, method_dir_name, model_dict, parse_args
 
 BASELINES = ('baseline', 'baseline++')
 METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet')
@@ -28,8 +28,8 @@ def check_method(method):
 
 def checkpoint_dir(p):
     """The directory train.main writes: <save_dir>/checkpoints/<dataset>/<model>_<method>[_aug][_<train_n_way>way_<n_shot>shot]
-    (the two baselines carry no way / shot suffix, train.py:176-180)."""
-    d = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, p.dataset, p.model, p.method)
+    (the two baselines carry no way / shot suffix, train.py:176-180; ``--head svm``: <method> reads metaoptnet_svm)."""
+    d = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, p.dataset, p.model, method_dir_name(p.method, getattr(p, "head", "ridge")))
     if p.train_aug:
         d += '_aug'
     if p.method not in BASELINES:

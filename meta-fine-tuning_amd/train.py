@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import configs, optim, parallel, settings, synthetic
-from .io_utils import get_assigned_file, model_dict, parse_args
+from .io_utils import get_assigned_file, method_dir_name, model_dict, parse_args
 from .methods import gnnnet_copy
 from .methods.gnnnet import GnnNet
 from .methods.matchingnet import MatchingNet
@@ -235,7 +235,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     if params.model == 'ResNet10_FW' and params.fine_tune:
         raise NotImplementedError("--model ResNet10_FW --fine_tune: the reference keeps the feature-wise noise on inside the inner loop, "
                                   "and the fused inner-loop kernels have no per-episode affine; meta-train ResNet10_FW without --fine_tune")
-    params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model, params.method)
+    params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model,
+                                                         method_dir_name(params.method, params.head))
     if params.train_aug:
         params.checkpoint_dir += '_aug'
     if params.method in ('baseline', 'baseline++'):                      # train.py:101-108,176-180
@@ -258,7 +259,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
         else:
             cls = gnnnet_copy.GnnNet if (variant50 and params.n_shot == 50) else GnnNet          # train_50.py:154-157
         torch.manual_seed(0) if W > 1 else None
-        model = cls(model_dict[params.model], n_way=params.train_n_way, n_support=params.n_shot).cuda()
+        kw = dict(head=params.head) if params.method == 'metaoptnet' else {}
+        model = cls(model_dict[params.model], n_way=params.train_n_way, n_support=params.n_shot, **kw).cuda()
         params.checkpoint_dir += '_%dway_%dshot' % (params.train_n_way, params.n_shot)
     os.makedirs(params.checkpoint_dir, exist_ok=True)
     if params.start_epoch > 0:
