@@ -5,187 +5,86 @@ missing, and every wrapper raises ``RuntimeError`` on a non-zero return code.
 """
 import ctypes
 import os
+import re
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libmft_hip.so")
 
 _P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_longlong
-_F = ctypes.c_float
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float}
 
-# name -> argtypes; every function returns int unless listed in _RESTYPE
-SIGNATURES = {
-    "mft_version": [],
-    "mft_device_info": [_P, _P],
-    "mft_stream_create_cumask": [_P, _I, _P],
-    "mft_stream_destroy": [_P],
-    "mft_stream_probe": [_P, _P, _P, _L, _P],
-    "mft_probe_placement": [_P, _I, _I, _P],
-    "mft_event_create": [_P],
-    "mft_event_record": [_P, _P],
-    "mft_event_elapsed_ms": [_P, _P, _P],
-    "mft_event_destroy": [_P],
-    "mft_augment_views": [_P, _I, _I, _I, _P, _I, _P, _L, _L, _I, _P, _P, _P],
-    "mft_nchw_to_nhwc": [_P, _P, _I, _I, _I, _I, _P],
-    "mft_pack_oihw": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "mft_unpack_oihw": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "mft_pack_dgrad": [_P, _P, _I, _I, _I, _I, _I, _L, _L, _P],
-    "mft_conv2d_nhwc": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P],
-    "mft_has_experiments": [],
-    "mft_split_bf16x3": [_P, _P, _L, _P],
-    "mft_split_bf16x3_multi": [_P, _I, _L, _P],
-    "mft_conv2d_nhwc_x3": [_P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mft_conv2d_x3_stats_ws_floats": [_I, _I, _I, _I, _I, _I, _I, _I],
-    "mft_conv2d_nhwc_x3_bnstats": [_P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "mft_conv2d_dgrad_nhwc": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P],
-    "mft_conv_ksplit_ws_floats": [_L, _I, _I],
-    "mft_conv_ksplit_grouped_ws_floats": [_L, _I, _I, _I],
-    "mft_conv2d_nhwc_ksplit_grouped": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P],
-    "mft_conv2d_dgrad_nhwc_ksplit_grouped": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P],
-    "mft_conv2d_nhwc_ksplit": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "mft_conv2d_dgrad_nhwc_ksplit": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "mft_conv2d_wgrad_oihw_ws_floats": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "mft_conv2d_wgrad_oihw": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "mft_conv2d_wgrad_oihw_multi": [_P, _I, _P],
-    "mft_conv2d_wgrad_ws_floats": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "mft_conv2d_wgrad_nhwc": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P],
-    "mft_conv2d_wgrad_adam_nhwc": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F,
-                                   _F, _P],
-    "mft_pair_softmax_ut_backward": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "mft_pair_bwd_stats_ws_floats": [_L, _I],
-    "mft_pair_bn_act_backward": [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _L, _I, _L, _F, _P, _P, _P, _P, _P, _P],
-    "mft_pair_absdiff_ut": [_P, _I, _P, _P, _I, _I, _I, _L, _L, _P],
-    "mft_pair_dx_gather": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _L, _L, _P],
-    "mft_pack_oihw_multi": [_P, _I, _L, _P],
-    "mft_wgrad_adam_next_forward": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _P, _F, _F, _F,
-                                    _F, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P],
-    "mft_bn_stats_ws_floats": [_I, _I, _I],
-    "mft_bn_stats": [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _F, _P, _P],
-    "mft_bn_apply": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _I, _F, _P],
-    "mft_bn_apply_multi": [_P, _I, _P],
-    "mft_bn_stats_multi": [_P, _I, _P],
-    "mft_bn_relu_maxpool": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "mft_bn_relu_maxpool_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "mft_bn_image_moments": [_P, _I, _I, _I, _L, _P, _P, _P],
-    "mft_bn_combine_moments": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
-    "mft_global_avgpool": [_P, _P, _I, _I, _I, _P],
-    "mft_bn_small_forward": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _F, _F, _P, _I, _P],
-    "mft_bn_backward2": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P],
-    "mft_ce_pool_backward": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mft_bn_backward": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
-    "mft_avgpool_relu_backward": [_P, _P, _P, _I, _I, _I, _P],
-    "mft_cross_entropy": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
-    "mft_softmax_rows": [_P, _I, _P, _I, _I, _I, _P],
-    "mft_proto_scores": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "mft_proto_backward": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
-    "mft_mn_gemm": [_I, _I, _I, _I, _I, _P, _I, _L, _P, _P, _I, _L, _I, _P, _I, _L, _P, _I, _L, _I, _P, _I, _L, _P, _P, _P, _I, _L, _P],
-    "mft_lstm_step_forward": [_P, _I, _L, _P, _I, _L, _P, _I, _P, _P, _I, _L, _I, _I, _I, _P],
-    "mft_lstm_step_backward": [_P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _P, _I, _L, _P, _P, _I, _I, _I, _I, _P],
-    "mft_mn_gather": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mft_mn_scatter_backward": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
-    "mft_mn_encode_combine": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
-    "mft_mn_colsum": [_P, _I, _I, _L, _P, _P],
-    "mft_mn_attention_forward": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "mft_mn_attention_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "mft_mn_readout_forward": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "mft_mn_readout_backward": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mft_nll_mean": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
-    "mft_nll_mean_backward": [_P, _I, _I, _I, _P, _P, _I, _P],
-    "mft_ridge_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P],
-    "mft_ridge_factor_solve": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mft_ridge_scores": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
-    "mft_ridge_backward_query": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
-    "mft_ridge_backward_support": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "mft_svm_gram": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "mft_svm_solve": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "mft_svm_backward_support": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "mft_dist_linear_forward": [_P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P],
-    "mft_dist_linear_backward": [_P, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _P],
-    "mft_dist_head_sgd_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P],
-    "mft_dist_head_step": [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _F, _P],
-    "mft_cross_entropy_mean": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
-    "mft_cross_entropy_mean_backward": [_P, _I, _P, _I, _I, _I, _P, _P, _I, _P],
-    "mft_adam_step": [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P],
-    "mft_sgd_step": [_P, _P, _P, _L, _I, _F, _F, _F, _F, _P],
-    "mft_maml_delta": [_P, _P, _P, _L, _P],
-    "mft_conv2d_wgrad_adam_dgrad_ws_floats": [_I, _I, _I, _I],
-    "mft_conv2d_wgrad_adam_dgrad_nhwc": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F, _F, _P],
-    "mft_conv2d_wgrad_adam_dgrad_nhwc_dev": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P, _F, _F, _F, _P],
-    "mft_col2im_bn_backward_small": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
-    "mft_stream_create_priority": [_I, _P, _P],
-    "mft_ce_pool_bn_backward2": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P],
-    "mft_pool_window_minmax": [_P, _P, _P, _L, _I, _I, _I, _P],
-    "mft_stem_cache_fill": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "mft_conv2d_nhwc_x3_bnin_bnstats": [_P, _I, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "mft_split_f16x2": [_P, _P, _L, _P],
-    "mft_conv2d_nhwc_h2": [_P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mft_conv2d_nhwc_h2_bnstats": [_P, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "mft_conv2d_nhwc_h2_bnin_bnstats": [_P, _I, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "mft_bn_apply_x3ws": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P],
-    "mft_bn_apply_x3ws_fits": [_I, _I, _I],
-    "mft_bn_running_ema": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _F, _F, _P, _P, _P],
-    "mft_bn_relu_pooled_gather_moments": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P],
-    "mft_bn_relu_pooled_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "mft_ingest_episode_views": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "mft_block_entry_small_forward": [_P, _I, _P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _F, _P],
-    "mft_block_exit_small_forward": [_P, _P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _P],
-    "mft_conv2d_dgrad_bn_backward_small": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _L,
-                                           _P, _P, _P],
-    "mft_linear_head_sgd_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _P],
-    "mft_linear_head_adam_run": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _F, _P],
-    "mft_adam_multi": [_P, _I, _I, _F, _F, _F, _F, _F, _F, _P],
-    "mft_adam_hyper_advance": [_P, _P, _F, _F, _F, _P],
-    "mft_adam_step_dev": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P],
-    "mft_conv2d_wgrad_adam_nhwc_dev": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P, _F, _F,
-                                       _F, _P],
-    "mft_linear_head_step": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _F, _P],
-    "mft_linear_head_scores": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mft_pair_absdiff": [_P, _I, _P, _I, _I, _I, _I, _P],
-    "mft_masked_softmax": [_P, _I, _P, _I, _I, _P],
-    "mft_pair_mlp_tiles_m": [_I, _I],
-    "mft_pair_mlp_layer": [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P],
-    "mft_bn_forward_small": [_P, _P],
-    "mft_bn_forward_small_max_rows": [],
-    "mft_gemm_rk": [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P],
-    "mft_pair_mlp_tiles_m_rk": [_I, _I],
-    "mft_pair_mlp_layer_rk": [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "mft_pair_mlp_stats_finalize_rk": [_P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P],
-    "mft_pair_mlp_stats_finalize": [_P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P],
-    "mft_pair_mlp_score": [_P, _I, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P],
-    "mft_masked_softmax_ut": [_P, _P, _I, _I, _P],
-    "mft_graph_aggregate": [_P, _P, _I, _P, _I, _I, _I, _I, _P],
-    "mft_copy_cols": [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P],
-    "mft_build_graph_nodes": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "mft_gather_query_scores": [_P, _I, _P, _I, _I, _I, _I, _P],
-    "mft_gather_rows": [_P, _P, _P, _I, _L, _P],
-    "mft_var_to_rstd": [_P, _P, _I, _F, _P],
-    "mft_bn_backward_ws_floats": [_I, _I, _I],
-    "mft_bn_backward_act": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _I, _F, _P, _P, _P, _P, _P],
-    "mft_bn_backward_act_multi": [_P, _I, _P],
-    "mft_act_backward": [_P, _I, _P, _I, _P, _I, _I, _L, _I, _F, _I, _P],
-    "mft_colsum": [_P, _I, _I, _L, _P, _P, _P],
-    "mft_bn_relu_maxpool_arg": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "mft_maxpool_relu_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "mft_masked_softmax_backward": [_P, _P, _P, _I, _I, _I, _P],
-    "mft_pair_absdiff_backward": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
-    "mft_graph_aggregate_backward": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
-    "mft_build_graph_nodes_backward": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "mft_gather_query_scores_backward": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "mft_fwt_draw_fold": [_P, _I, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _P, _P],
-    "mft_fwt_unfold": [_P, _I, _I, _I, _P, _P],
-    "mft_episode_top1": [_P, _I, _I, _I, _I, _P, _P, _P],
-}
+
+def _ctype(decl, where):
+    """ctypes class of one C declaration ``TYPE name``: any pointer is a c_void_p, a scalar must be one of _SCALARS."""
+    if "*" in decl:
+        return _P
+    ctype = _SCALARS.get(" ".join(w for w in decl.split()[:-1] if w != "const"))
+    if ctype is None:
+        raise RuntimeError("%s: cannot bind `%s` (scalars the binding knows: %s)" % (where, decl, ", ".join(_SCALARS)))
+    return ctype
+
+
+def parse_header(text):
+    """C header text -> ({function: (argtypes, restype)}, {struct typedef: _fields_}).  Every statement that is left after the
+    comments, preprocessor lines, enums and struct typedefs are taken out must be a prototype ``RET mft_name(ARGS);`` over
+    pointers and the _SCALARS; anything else raises -- the binding never guesses."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r'^\s*#.*$|extern\s+"C"\s*\{|enum\s*\w*\s*\{[^}]*\}\s*;', " ", text, flags=re.M)
+    protos, structs = {}, {}
+
+    def take_struct(m):
+        name, fields = m.group(2), []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(1).split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            if "*" in decl and more:
+                raise RuntimeError("struct %s: one pointer per declaration, got `%s`" % (name, decl))
+            ctype = _ctype(first, "struct " + name)
+            fields += [(n, ctype) for n in [re.split(r"[\s*]+", first)[-1]] + more]
+        if name in structs:
+            raise RuntimeError("struct %s is declared twice" % name)
+        structs[name] = fields
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, text, flags=re.S)
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        if stmt == "}":                                    # closes extern "C"
+            continue
+        m = re.fullmatch(r"([^()]+?)\b(mft_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            raise RuntimeError("not a prototype the binding understands: `%s`" % stmt)
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if name in protos:
+            raise RuntimeError("%s is declared twice" % name)
+        argtypes = [] if args in ("", "void") else [_ctype(a, name) for a in args.split(",")]
+        protos[name] = (argtypes, None if ret == "void" else _ctype(ret + " " + name, name))
+    if not protos:
+        raise RuntimeError("no prototype found in the header")
+    return protos, structs
+
+
+def _load_header(name):
+    with open(os.path.join(os.path.dirname(PKG), "include", name)) as f:
+        return parse_header(f.read())
+
+
+# include/mft_hip.h is the one copy of the ABI.  SIGNATURES: launcher -> argtypes; RESTYPES: launcher or hook -> restype (None = void)
+_protos, _STRUCT_FIELDS = _load_header("mft_hip.h")
 # test / A-B hooks (include/mft_hip_testing.h): form selection for tests/ and tools/, never called by the product path
-TESTING_SIGNATURES = {
-    "mft_debug_set_conv_tile": [_I],
-    "mft_debug_set_x3_tile": [_I],
-    "mft_debug_reset": [],
-    "mft_wgrad_fwd_set_exact": [_I],
-    "mft_wgrad_fwd_set_xcd": [_I],
-}
-_RESTYPE = {"mft_conv2d_x3_stats_ws_floats": _L, "mft_bn_stats_ws_floats": _L, "mft_conv2d_wgrad_ws_floats": _L, "mft_bn_backward_ws_floats": _L,
-            "mft_conv2d_wgrad_adam_dgrad_ws_floats": _L, "mft_pair_bwd_stats_ws_floats": _L, "mft_conv_ksplit_ws_floats": _L, "mft_conv2d_wgrad_oihw_ws_floats": _L, "mft_conv_ksplit_grouped_ws_floats": _L}
+_hooks = _load_header("mft_hip_testing.h")[0]
+if set(_protos) & set(_hooks):
+    raise RuntimeError("declared in both headers: %s" % sorted(set(_protos) & set(_hooks)))
+SIGNATURES = {n: a for n, (a, _) in _protos.items()}
+TESTING_SIGNATURES = {n: a for n, (a, _) in _hooks.items()}
+RESTYPES = {n: r for n, (_, r) in list(_protos.items()) + list(_hooks.items())}
+_structs = {}
+
+
+def struct(name):
+    """The ctypes.Structure of a ``typedef struct`` of include/mft_hip.h (e.g. "MftBnFwdJob"): same field names, order and layout."""
+    if name not in _structs:
+        _structs[name] = type(name, (ctypes.Structure,), {"_fields_": _STRUCT_FIELDS[name]})
+    return _structs[name]
+
 
 _lib = None
 
@@ -209,7 +108,7 @@ def lib():
         for name, argtypes in list(SIGNATURES.items()) + list(TESTING_SIGNATURES.items()):
             fn = getattr(h, name)          # AttributeError if the .so lacks a declared symbol
             fn.argtypes = argtypes
-            fn.restype = _RESTYPE.get(name, _I)
+            fn.restype = RESTYPES[name]
         _lib = h
     return _lib
 
@@ -220,6 +119,23 @@ MFT_EINVAL = -22
 def check(rc, what):
     if rc != 0:
         raise RuntimeError("%s failed with code %d (hipError_t / MFT_EINVAL=-22)" % (what, rc))
+
+
+def call(name, *args):
+    """Run launcher ``name`` of ``lib()`` (a running LaunchTimer stands in); a non-zero status raises."""
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        check(rc, name)
+
+
+def try_call(name, *args):
+    """``call`` for a launcher with a fallback: False on MFT_EINVAL (outside its domain, nothing ran: the caller takes the other
+    route), True on success; any other status raises."""
+    rc = getattr(lib(), name)(*args)
+    if rc == MFT_EINVAL:
+        return False
+    check(rc, name)
+    return True
 
 
 class LaunchTimer:

@@ -162,9 +162,8 @@ def augment_views(src_u8, params, size, out=None, view_stride=None, img_stride=N
         view_stride, img_stride = n_img * size * size * 3, size * size * 3
     mean = (ctypes.c_float * 3)(*IMAGENET_MEAN)
     std = (ctypes.c_float * 3)(*IMAGENET_STD)
-    rc = _lib.lib().mft_augment_views(ops._p(src_u8), n_img, Hs, Ws, ops._p(p), n_views, ops._p(out), view_stride, img_stride,
-                                      size, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), ops._stream())
-    _lib.check(rc, "mft_augment_views")
+    _lib.call("mft_augment_views", ops._p(src_u8), n_img, Hs, Ws, ops._p(p), n_views, ops._p(out), view_stride, img_stride, size,
+              ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), ops._stream())
     return out
 
 

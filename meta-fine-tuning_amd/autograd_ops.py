@@ -60,12 +60,10 @@ def _running(mod):
 def _eval_weights(mod, W):
     """Eval-mode BatchNorm: statistics come from the running buffers."""
     stats = {}
-    lib = ops._lib.lib()
     for name, m in mod.named_modules():
         if isinstance(m, torch.nn.BatchNorm2d):
             rstd = torch.empty_like(m.running_var)
-            ops._lib.check(lib.mft_var_to_rstd(ops._p(m.running_var), ops._p(rstd), rstd.numel(), m.eps, ops._stream()),
-                           "mft_var_to_rstd")
+            ops._lib.call("mft_var_to_rstd", ops._p(m.running_var), ops._p(rstd), rstd.numel(), m.eps, ops._stream())
             stats[name] = (m.running_mean.view(1, -1), rstd.view(1, -1))
     return stats
 
@@ -210,9 +208,8 @@ class _CrossEntropyFn(torch.autograd.Function):
     def forward(ctx, logits, target, loss_sum):
         rows, C = logits.shape
         loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        lib = ops._lib.lib()
-        ops._lib.check(lib.mft_cross_entropy_mean(ops._p(logits), logits.stride(0), ops._p(target), 1 if target.dtype == torch.int64 else 0,
-                                                  C, rows, ops._p(loss), ops._p(loss_sum), ops._stream()), "mft_cross_entropy_mean")
+        ops._lib.call("mft_cross_entropy_mean", ops._p(logits), logits.stride(0), ops._p(target), 1 if target.dtype == torch.int64 else 0,
+                      C, rows, ops._p(loss), ops._p(loss_sum), ops._stream())
         ctx.save_for_backward(logits, target)
         return loss
 
@@ -222,10 +219,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         rows, C = logits.shape
         d = torch.empty((rows, C), device=logits.device, dtype=torch.float32)
         g = g.contiguous().float()
-        lib = ops._lib.lib()
-        ops._lib.check(lib.mft_cross_entropy_mean_backward(ops._p(logits), logits.stride(0), ops._p(target),
-                                                           1 if target.dtype == torch.int64 else 0, C, rows, ops._p(g), ops._p(d), C,
-                                                           ops._stream()), "mft_cross_entropy_mean_backward")
+        ops._lib.call("mft_cross_entropy_mean_backward", ops._p(logits), logits.stride(0), ops._p(target),
+                      1 if target.dtype == torch.int64 else 0, C, rows, ops._p(g), ops._p(d), C, ops._stream())
         return d, None, None
 
 

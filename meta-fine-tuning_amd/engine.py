@@ -211,14 +211,12 @@ class AdaptState:
                 c.zero_()
             del ballast
             n = total // 1024 * 1024
-            lib = ops._lib.lib()
 
             def rate(t, reps):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
                 for _ in range(reps):
-                    ops._lib.check(lib.mft_stream_probe(ops._p(cands[t[0]]), ops._p(cands[t[1]]), ops._p(cands[t[2]]), n,
-                                                        ops._stream()), "mft_stream_probe")
+                    ops._lib.call("mft_stream_probe", ops._p(cands[t[0]]), ops._p(cands[t[1]]), ops._p(cands[t[2]]), n, ops._stream())
                 b.record()
                 b.synchronize()
                 return 24.0 * n * reps / (a.elapsed_time(b) * 1e-3) / 1e9
@@ -408,7 +406,7 @@ class FinetuneEngine:
         if pipeline and prio > 0:              # below torch's range: a HIP stream at the device's least priority
             out = ctypes.c_void_p()
             with torch.cuda.device(self.dev):
-                ops._lib.check(ops._lib.lib().mft_stream_create_priority(prio, ctypes.byref(out), None), "mft_stream_create_priority")
+                ops._lib.call("mft_stream_create_priority", prio, ctypes.byref(out), None)
             self._raw_stream = out.value
             self.s_trunk = torch.cuda.ExternalStream(out.value, device=self.dev)
         elif pipeline:
@@ -448,10 +446,8 @@ class FinetuneEngine:
             views += [xv.to(self.dev, non_blocking=True) for xv in liz_x[1:]]
         views = [v if (v.dtype == torch.float32 and v.is_contiguous()) else v.float().contiguous() for v in views]
         ptrs = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-        rc = ops._lib.lib().mft_ingest_episode_views(ptrs, len(views), 1 if self.views else 0, self.n_way,
-                                                     ns + self.n_query, ns, 3, H, H, ops._p(Xs[slot * self.n_total]),
-                                                     ops._p(Xall[slot * self.n_all]), ops._stream())
-        ops._lib.check(rc, "mft_ingest_episode_views")
+        ops._lib.call("mft_ingest_episode_views", ptrs, len(views), 1 if self.views else 0, self.n_way, ns + self.n_query, ns, 3, H, H,
+                      ops._p(Xs[slot * self.n_total]), ops._p(Xall[slot * self.n_all]), ops._stream())
 
     @_on_device
     def load_episode_source(self, slot, src_u8, params, Xs=None, Xall=None):
@@ -541,11 +537,8 @@ class FinetuneEngine:
             c = self.cls
             dlogits = self.arena.get("lin.dfeat%d" % k, (E * k, 512))
             loss = self.arena.get("lin.loss", (E,))
-            rc = ops._lib.lib().mft_linear_head_step(ops._p(feat), 512, ops._p(lab_dev), k, E, self.n_way, 512, ops._p(c["W"]),
-                                                     ops._p(c["b"]), ops._p(c["mW"]), ops._p(c["vW"]), ops._p(c["mb"]),
-                                                     ops._p(c["vb"]), ops._p(dlogits), 512, ops._p(loss), self.adapt.step,
-                                                     self.lr, 0.9, 0.999, 1e-8, 0.001, ops._stream())
-            ops._lib.check(rc, "mft_linear_head_step")
+            ops.linear_head_step(feat, lab_dev, c["W"], c["b"], c["mW"], c["vW"], c["mb"], c["vb"], self.adapt.step, dfeat=dlogits,
+                                 loss=loss, lr=self.lr, weight_decay=0.001)
             ce = None
         elif self.mode == "dist":
             # the same step with the cosine head: scores, CE, d feature (pre-update V, g), Adam(lr .01, wd .001) on V, g in one launch
@@ -731,9 +724,7 @@ class FinetuneEngine:
             # finetune.py:165-174: features of cat(support, query) in one train-mode pass (BatchNorm statistics over all
             # n_all images are order independent), classifier + softmax on the query rows (class-major)
             sc = arena.get("lin.scores", (self.E * self.n_all, self.n_way))
-            rc = ops._lib.lib().mft_linear_head_scores(ops._p(feats), 512, self.n_all, self.E, self.n_way, 512,
-                                                       ops._p(self.cls["W"]), ops._p(self.cls["b"]), ops._p(sc), ops._stream())
-            ops._lib.check(rc, "mft_linear_head_scores")
+            ops.linear_head_scores(feats, self.cls["W"], self.cls["b"], out=sc)
             sc = sc.view(self.E, self.n_way, self.n_support + self.n_query, self.n_way)[:, :, self.n_support:]
             return sc.reshape(self.E, self.n_way * self.n_query, self.n_way), feats
         if self.mode == "dist":
@@ -975,12 +966,11 @@ def _adapt_body(st, feature_mod, plan, n, H, lr):
         h7 = x6_of[0].shape[1]
         h7 = (h7 + 2 - 3) // 2 + 1
         rows = [k * h7 * h7 for k in st.kinds] + [1]
-        lib = ops._lib.lib()
         for nm, bn in (("bn1", "trunk.7.BN1"), ("bn2", "trunk.7.BN2"), ("bns", "trunk.7.BNshortcut")):
             m, r = sink[nm]
             rm, rv = running[bn]
-            ops._lib.check(lib.mft_bn_running_ema(ops._p(m), ops._p(r), rows[0], ops._p(m), ops._p(r), rows[1], ops._p(st.order_steps),
-                                                  n_steps, 512, ops.BN_EPS, 0.1, ops._p(rm), ops._p(rv), ops._stream()), "mft_bn_running_ema")
+            ops._lib.call("mft_bn_running_ema", ops._p(m), ops._p(r), rows[0], ops._p(m), ops._p(r), rows[1], ops._p(st.order_steps),
+                          n_steps, 512, ops.BN_EPS, 0.1, ops._p(rm), ops._p(rv), ops._stream())
         return ad.w.export(0)
     # frozen trunk.0-6 of step t+1 on a second stream while the last block of step t is adapted (as in FinetuneEngine)
     s_trunk = _ADAPT_STREAMS.get(dev)
@@ -1015,7 +1005,6 @@ def _adapt_body(st, feature_mod, plan, n, H, lr):
 def _trunk_running_ema(st, arena_t, running, H):
     """running_mean / running_var of the nine BatchNorms of trunk.1-6 after the episode's steps, from the per-group statistics the
     grouped passes left in the arena (one launch per layer)."""
-    lib = ops._lib.lib()
     oh0 = (H + 6 - 7) // 2 + 1
     sp = {4: (oh0 + 2 - 3) // 2 + 1}
     sp[5] = (sp[4] + 2 - 3) // 2 + 1
@@ -1037,8 +1026,8 @@ def _trunk_running_ema(st, arena_t, running, H):
         if len(sets) == 1:
             sets.append((None, None, 1))
         (ma, ra, na), (mb, rb, nb) = sets
-        ops._lib.check(lib.mft_bn_running_ema(ops._p(ma), ops._p(ra), na, ops._p(mb), ops._p(rb), nb, ops._p(st.order), st.order.numel(), C,
-                                              ops.BN_EPS, 0.1, ops._p(rm), ops._p(rv), ops._stream()), "mft_bn_running_ema")
+        ops._lib.call("mft_bn_running_ema", ops._p(ma), ops._p(ra), na, ops._p(mb), ops._p(rb), nb, ops._p(st.order), st.order.numel(), C,
+                      ops.BN_EPS, 0.1, ops._p(rm), ops._p(rv), ops._stream())
 
 
 def refuse_feature_wise(what, who):

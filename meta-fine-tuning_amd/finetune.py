@@ -263,14 +263,8 @@ def _finetune_linear_frozen(P, x0, state_in, n_way, n_support, n_query, classifi
             steps.append(np.concatenate([ids, -np.ones(batch_size - len(ids), dtype=ids.dtype)]))
     table = torch.from_numpy(np.stack(steps).astype(np.int32)).cuda()
     y_dev = torch.from_numpy(np.repeat(np.arange(n_way), n_support).astype(np.int32)).cuda()
-    D = za.shape[1]
-    rc = ops._lib.lib().mft_linear_head_adam_run(ops._p(za), ops._p(y_dev), ops._p(table), 1, support_size, D, n_way, table.shape[0],
-                                                 batch_size, ops._p(W), ops._p(b), 0.01, 0.9, 0.999, 1e-8, 0.001, ops._stream())
-    ops._lib.check(rc, "mft_linear_head_adam_run")
-    out = torch.empty((zb.shape[0], n_way), device=zb.device)      # softmax(zb @ W^T + b): one group of all query rows
-    rc = ops._lib.lib().mft_linear_head_scores(ops._p(zb), D, zb.shape[0], 1, n_way, D, ops._p(W), ops._p(b), ops._p(out), ops._stream())
-    ops._lib.check(rc, "mft_linear_head_scores")
-    return out
+    ops.linear_head_adam_run(za[None], y_dev[None], table[None], W, b, lr=0.01, weight_decay=0.001)
+    return ops.linear_head_scores(zb, W, b)                          # softmax(zb @ W^T + b): one group of all query rows
 
 
 def _finetune_linear(P, liz_x, y, state_in, save_it, linear=False, flatten=True, n_query=15, ds=False,

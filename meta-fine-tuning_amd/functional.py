@@ -297,9 +297,8 @@ def _bn_stats4(arena, tag, x, ipg, groups, running=None, fixed=None):
     rm = rv = nbt = None
     if running is not None:
         rm, rv, nbt = running if len(running) == 3 else (running + (None,))
-    rc = ops._lib.lib().mft_bn_stats(ops._p(x), C, C, rows, groups, ops.BN_EPS, ops._p(mean), ops._p(rstd), ops._p(ws),
-                                     ops._p(rm), ops._p(rv), 0.1, ops._p(nbt), ops._stream())
-    ops._lib.check(rc, "mft_bn_stats")
+    ops._lib.call("mft_bn_stats", ops._p(x), C, C, rows, groups, ops.BN_EPS, ops._p(mean), ops._p(rstd), ops._p(ws), ops._p(rm),
+                  ops._p(rv), 0.1, ops._p(nbt), ops._stream())
     return mean, rstd
 
 
@@ -352,16 +351,13 @@ class StemCache:
 
     def fill(self, x_nhwc):
         """x_nhwc [n_slots,H,H,3] -> conv outputs + moments (chunked launches; M = chunk*OH*OW rows each)."""
-        lib = ops._lib.lib()
         n = x_nhwc.shape[0]
         assert n == self.n_slots
         if self.fused_fill:
             # ONE launch: convolution + per-image moments + per-window (max, min); the full-resolution output never reaches HBM
             wpk = self.W.conv["trunk.0"]
-            rc = lib.mft_stem_cache_fill(ops._p(x_nhwc), ops._p(wpk), wpk.shape[-1], n, x_nhwc.shape[1], x_nhwc.shape[2],
-                                         ops._p(self.pmax), ops._p(self.pmin), ops._p(self.mean), ops._p(self.m2), ops._stream())
-            if rc != ops._lib.MFT_EINVAL:
-                ops._lib.check(rc, "mft_stem_cache_fill")
+            if ops._lib.try_call("mft_stem_cache_fill", ops._p(x_nhwc), ops._p(wpk), wpk.shape[-1], n, x_nhwc.shape[1], x_nhwc.shape[2],
+                                 ops._p(self.pmax), ops._p(self.pmin), ops._p(self.mean), ops._p(self.m2), ops._stream()):
                 return
             self.fused_fill = False                                   # outside the kernel's domain: the three launches from now on
             self._buf = torch.empty((self.chunk, self.OH, self.OH, 64), device=x_nhwc.device)
@@ -369,19 +365,17 @@ class StemCache:
             j = min(i + self.chunk, n)
             c0 = self._buf[:j - i] if self.pooled else self.c0[i:j]
             ops.conv2d(x_nhwc[i:j], self.W.conv["trunk.0"], 64, 7, 7, 2, 3, out=c0)
-            ops._lib.check(lib.mft_bn_image_moments(ops._p(c0), 64, 64, self.OH * self.OH, j - i,
-                                                    ops._p(self.mean[i:j]), ops._p(self.m2[i:j]), ops._stream()),
-                           "mft_bn_image_moments")
+            ops._lib.call("mft_bn_image_moments", ops._p(c0), 64, 64, self.OH * self.OH, j - i, ops._p(self.mean[i:j]),
+                          ops._p(self.m2[i:j]), ops._stream())
             if self.pooled:
-                ops._lib.check(lib.mft_pool_window_minmax(ops._p(c0), ops._p(self.pmax[i:j]), ops._p(self.pmin[i:j]), j - i,
-                                                          self.OH, self.OH, 64, ops._stream()), "mft_pool_window_minmax")
+                ops._lib.call("mft_pool_window_minmax", ops._p(c0), ops._p(self.pmax[i:j]), ops._p(self.pmin[i:j]), j - i, self.OH,
+                              self.OH, 64, ops._stream())
 
     def gather(self, idx, n, m, s, g, b, ipg, out):
         """BN + ReLU + MaxPool of images idx with the mini-batch statistics (m, s) -> out [n, PH, PH, 64]."""
         if self.pooled:
-            ops._lib.check(ops._lib.lib().mft_bn_relu_pooled_gather(ops._p(self.pmax), ops._p(self.pmin), ops._p(idx), ops._p(out), n,
-                                                                    self.PH, self.PH, 64, ipg, ops._p(m), ops._p(s), ops._p(g),
-                                                                    ops._p(b), ops._stream()), "mft_bn_relu_pooled_gather")
+            ops._lib.call("mft_bn_relu_pooled_gather", ops._p(self.pmax), ops._p(self.pmin), ops._p(idx), ops._p(out), n, self.PH, self.PH,
+                          64, ipg, ops._p(m), ops._p(s), ops._p(g), ops._p(b), ops._stream())
             return out
         assert self.c0 is not None, "this path needs the full-resolution stem cache (StemCache(pooled=False))"
         return ops.bn_relu_maxpool_gather(self.c0, idx, n, m, s, g, b, ipg, out=out)
@@ -390,10 +384,9 @@ class StemCache:
         """gather() with the mini-batch statistics combined from the cached per-image moments in the same launch."""
         assert self.pooled
         m, s = stats if stats is not None else (None, None)
-        ops._lib.check(ops._lib.lib().mft_bn_relu_pooled_gather_moments(
-            ops._p(self.pmax), ops._p(self.pmin), ops._p(idx), ops._p(out), n, self.PH, self.PH, 64, ipg, ops._p(self.mean),
-            ops._p(self.m2), self.OH * self.OH, ops.BN_EPS, ops._p(g), ops._p(b), ops._p(m), ops._p(s), ops._stream()),
-            "mft_bn_relu_pooled_gather_moments")
+        ops._lib.call("mft_bn_relu_pooled_gather_moments", ops._p(self.pmax), ops._p(self.pmin), ops._p(idx), ops._p(out), n, self.PH,
+                      self.PH, 64, ipg, ops._p(self.mean), ops._p(self.m2), self.OH * self.OH, ops.BN_EPS, ops._p(g), ops._p(b), ops._p(m),
+                      ops._p(s), ops._stream())
         return out
 
 
@@ -446,11 +439,9 @@ def _bn_small(arena, tag, x1, g1, b1, rows, groups, C, gbs, out, x2=None, g2=Non
     m2 = s2 = None
     if x2 is not None:
         m2, s2 = stats2 if stats2 is not None else (arena.get(tag + ".mean2", (groups, C)), arena.get(tag + ".rstd2", (groups, C)))
-    rc = ops._lib.lib().mft_bn_small_forward(ops._p(x1), C, ops._p(x2), C, ops._p(res), C, ops._p(out), C, C, rows, groups,
-                                             ops._p(g1), ops._p(b1), ops._p(g2), ops._p(b2), gbs, ops._p(m1), ops._p(s1),
-                                             ops._p(m2), ops._p(s2), ops.ACT_RELU, 0.0, ops.BN_EPS, ops._p(pooled), hw,
-                                             ops._stream())
-    ops._lib.check(rc, "mft_bn_small_forward")
+    ops._lib.call("mft_bn_small_forward", ops._p(x1), C, ops._p(x2), C, ops._p(res), C, ops._p(out), C, C, rows, groups, ops._p(g1),
+                  ops._p(b1), ops._p(g2), ops._p(b2), gbs, ops._p(m1), ops._p(s1), ops._p(m2), ops._p(s2), ops.ACT_RELU, 0.0, ops.BN_EPS,
+                  ops._p(pooled), hw, ops._stream())
     return m1, s1, m2, s2
 
 
@@ -496,37 +487,35 @@ def simple_block(W, p, x, arena, ipg, cin, cout, stride, running=None, tag="b", 
         c1 = arena.get(tag + ".c1", (n, OH, OH, cout))
         r1 = arena.get(tag + ".r1", (n * OH * OH, cout))
         sc = arena.get(tag + ".sc", (n, OH, OH, cout))
-        rc = ops._lib.MFT_EINVAL
+        fused = False
         # (one group = a single episode: the weight-streaming kernels would run on a handful of workgroups; the K-sliced
         #  implicit GEMM + one small BatchNorm launch is several times faster there)
         if FUSED_LAST_BLOCK and c1w.dim() == 3 and scw.dim() == 3 and groups > ops.SMALL_GROUPS and not so:
             # C1 + BatchNorm + ReLU and the shortcut convolution (which samples C1's centre tap) in one launch
             m1 = arena.get(tag + ".bn1.mean", (groups, cout))
             s1 = arena.get(tag + ".bn1.rstd", (groups, cout))
-            rc = ops._lib.lib().mft_block_entry_small_forward(
+            fused = ops._lib.try_call(
+                "mft_block_entry_small_forward",
                 ops._p(x), x.shape[-1], ops._p(c1w), c1w.shape[1] * c1w.shape[2], ops._p(scw), scw.shape[1] * scw.shape[2],
                 ops._p(c1), ops._p(r1), ops._p(sc), n, H, Wd, cin, cout, stride, ipg, ops._p(g1), ops._p(b1), gbs, ops._p(m1),
                 ops._p(s1), ops.BN_EPS, ops._stream())
-            if rc != ops._lib.MFT_EINVAL:
-                ops._lib.check(rc, "mft_block_entry_small_forward")
-        if rc == ops._lib.MFT_EINVAL:                      # outside the fused kernel's domain: three launches
+        if not fused:                                      # outside the fused kernel's domain: three launches
             conv(".C1", x, c1w, 3, stride, 1, c1)
             m1, s1, _, _ = _bn_small(arena, tag + ".bn1", c1, g1, b1, rows, groups, cout, gbs, r1, stats=so.get("bn1"))
             conv(".shortcut", x, scw, 1, stride, 0, sc)
         r1 = r1.view(n, OH, OH, cout)
         c2 = arena.get(tag + ".c2", (n, OH, OH, cout))
         out = arena.get(tag + ".out", (n * OH * OH, cout))
-        rc = ops._lib.MFT_EINVAL
+        fused = False
         if FUSED_LAST_BLOCK and pooled is not None and c2w.dim() == 3 and groups > ops.SMALL_GROUPS and not so:
             # C2 + both BatchNorms + residual add + ReLU + global average pool in one launch
             m2, s2, ms, ss = (arena.get(tag + ".bn2." + k, (groups, cout)) for k in ("mean", "rstd", "mean2", "rstd2"))
-            rc = ops._lib.lib().mft_block_exit_small_forward(
+            fused = ops._lib.try_call(
+                "mft_block_exit_small_forward",
                 ops._p(r1), ops._p(c2w), c2w.shape[1] * c2w.shape[2], ops._p(sc), ops._p(c2), ops._p(out), ops._p(pooled), n, OH,
                 OH, cout, ipg, ops._p(g2), ops._p(b2), ops._p(gs), ops._p(bs), gbs, ops._p(m2), ops._p(s2), ops._p(ms),
                 ops._p(ss), ops.BN_EPS, ops._stream())
-            if rc != ops._lib.MFT_EINVAL:
-                ops._lib.check(rc, "mft_block_exit_small_forward")
-        if rc == ops._lib.MFT_EINVAL:
+        if not fused:
             conv(".C2", r1, c2w, 3, 1, 1, c2)
             m2, s2, ms, ss = _bn_small(arena, tag + ".bn2", c2, g2, b2, rows, groups, cout, gbs, out, x2=sc, g2=gs, b2=bs,
                                        pooled=pooled, hw=OH * OH, stats=so.get("bn2"), stats2=so.get("bns"))
@@ -638,8 +627,7 @@ def last_block_forward(W, a, arena, ipg, slab=None, tape=None, running=None, tag
     out = simple_block(W, "trunk.7", a, arena, ipg, 256, 512, 2, running, tag + ".trunk.7", slab=slab, tape=info, pooled=feat,
                        fixed=fixed, stats_out=stats_out)
     if not info.get("pooled", False):
-        ops._lib.check(ops._lib.lib().mft_global_avgpool(ops._p(out), ops._p(feat), n, out.shape[1] * out.shape[2], 512,
-                                                         ops._stream()), "mft_global_avgpool")
+        ops._lib.call("mft_global_avgpool", ops._p(out), ops._p(feat), n, out.shape[1] * out.shape[2], 512, ops._stream())
     return feat
 
 
@@ -654,23 +642,20 @@ def resnet10_forward(W, x, arena, ipg=0, slab=None, tape=None, running=None, tag
     return last_block_forward(W, a, arena, ipg, slab=slab, tape=tape, running=running, tag=tag, fixed=fixed)
 
 
-def _dgrad_c2_bn1(lib, tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd):
+def _dgrad_c2_bn1(tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd):
     """Data gradient of trunk.7.C2 followed by the BatchNorm1 + ReLU backward -> dc1 (separate pass over C2's weights)."""
     # dgrad of C2 must read the pre-update weights: it runs before the fused wgrad+Adam of C2
-    rc = ops._lib.MFT_EINVAL
+    fused = False
     if FUSED_LAST_BLOCK and n // ipg > ops.SMALL_GROUPS:
         # (one group -- a single episode, the meta-fine-tuning training loop: the weight-streaming kernel would run on 16 workgroups;
         #  the K-sliced implicit GEMM + the BatchNorm backward launches below take a sixth of its time)
         # data gradient of C2 with the BatchNorm1 + ReLU backward in its epilogue (dr1 is not materialised)
         dc1 = arena.get(tag + ".dc1", tuple(c1.shape))
         w2 = params.c2w
-        rc = lib.mft_conv2d_dgrad_bn_backward_small(ops._p(dc2), C, ops._p(w2), ops._p(dc1), C, n, oh, ow, C, C, 3, 3, 1, ipg,
-                                                    w2.shape[1] * w2.shape[2], ops._p(c1), ops._p(r1), ops._p(tape["m1"]),
-                                                    ops._p(tape["s1"]), ops._p(params.bn1g), C, ops._p(grads.bn1g),
-                                                    ops._p(grads.bn1b), ops._stream())
-        if rc != ops._lib.MFT_EINVAL:
-            ops._lib.check(rc, "mft_conv2d_dgrad_bn_backward_small")
-    if rc == ops._lib.MFT_EINVAL:
+        fused = ops._lib.try_call("mft_conv2d_dgrad_bn_backward_small", ops._p(dc2), C, ops._p(w2), ops._p(dc1), C, n, oh, ow, C, C, 3, 3, 1,
+                                  ipg, w2.shape[1] * w2.shape[2], ops._p(c1), ops._p(r1), ops._p(tape["m1"]), ops._p(tape["s1"]),
+                                  ops._p(params.bn1g), C, ops._p(grads.bn1g), ops._p(grads.bn1b), ops._stream())
+    if not fused:
         dr1 = ops.conv2d_dgrad(dc2, params.c2w, 512, 3, 3, 1, imgs_per_group=ipg, out=arena.get(tag + ".dr1", (n, oh, ow, C)))
         dc1 = bn_bwd(c1, dr1, tape["m1"], tape["s1"], params.bn1g, grads.bn1g, grads.bn1b, r1, "dc1")
     return dc1
@@ -706,7 +691,6 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
     n, oh, ow, C = out.shape
     groups = n // ipg
     rows = ipg * oh * ow
-    lib = ops._lib.lib()
     fused_ce = FUSED_LAST_BLOCK and ce is not None and C % 64 == 0 and ipg <= 16
     d_out = None
     if fused_ce:
@@ -716,19 +700,16 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
         # one launch (dfeat is not materialised)
         d_out = arena.get(tag + ".dout", (n, oh, ow, C))
         feat, labels, loss = ce
-        ops._lib.check(lib.mft_ce_pool_backward(ops._p(feat), ops._p(labels), ipg, groups, C, oh * ow, ops._p(out), ops._p(d_out),
-                                                ops._p(loss), ops._stream()), "mft_ce_pool_backward")
+        ops._lib.call("mft_ce_pool_backward", ops._p(feat), ops._p(labels), ipg, groups, C, oh * ow, ops._p(out), ops._p(d_out),
+                      ops._p(loss), ops._stream())
     else:
         d_out = arena.get(tag + ".dout", (n, oh, ow, C))
-        ops._lib.check(lib.mft_avgpool_relu_backward(ops._p(dfeat), ops._p(out), ops._p(d_out), n, oh * ow, C,
-                                                     ops._stream()), "mft_avgpool_relu_backward")
+        ops._lib.call("mft_avgpool_relu_backward", ops._p(dfeat), ops._p(out), ops._p(d_out), n, oh * ow, C, ops._stream())
 
     def bn_bwd(xraw, dy, mean, rstd, gamma, dgamma, dbeta, relu_out, name, need_dx=True):
         dx = arena.get(tag + "." + name, tuple(xraw.shape)) if need_dx else None
-        rc = lib.mft_bn_backward(ops._p(xraw), C, ops._p(dy), C, ops._p(relu_out), C, ops._p(dx), C, C, rows, groups,
-                                 ops._p(mean), ops._p(rstd), ops._p(gamma), C, ops._p(dgamma), ops._p(dbeta),
-                                 ops._stream())
-        ops._lib.check(rc, "mft_bn_backward")
+        ops._lib.call("mft_bn_backward", ops._p(xraw), C, ops._p(dy), C, ops._p(relu_out), C, ops._p(dx), C, C, rows, groups, ops._p(mean),
+                      ops._p(rstd), ops._p(gamma), C, ops._p(dgamma), ops._p(dbeta), ops._stream())
         return dx
 
     def wgrad(xin, dy, name, k, stride, pad):
@@ -745,19 +726,17 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
         feat, labels, loss = ce
         dc2 = arena.get(tag + ".dc2", tuple(c2.shape))
         dsc = arena.get(tag + ".dsc", tuple(sc.shape))
-        rc = lib.mft_ce_pool_bn_backward2(ops._p(feat), ops._p(labels), ipg, groups, C, oh * ow, ops._p(out), ops._p(c2), ops._p(sc),
-                                          ops._p(dc2), ops._p(dsc), ops._p(tape["m2"]), ops._p(tape["s2"]), ops._p(params.bn2g),
-                                          ops._p(tape["ms"]), ops._p(tape["ss"]), ops._p(params.bnsg), C, ops._p(grads.bn2g),
-                                          ops._p(grads.bn2b), ops._p(grads.bnsg), ops._p(grads.bnsb), ops._p(loss), ops._stream())
-        ops._lib.check(rc, "mft_ce_pool_bn_backward2")
+        ops._lib.call("mft_ce_pool_bn_backward2", ops._p(feat), ops._p(labels), ipg, groups, C, oh * ow, ops._p(out), ops._p(c2),
+                      ops._p(sc), ops._p(dc2), ops._p(dsc), ops._p(tape["m2"]), ops._p(tape["s2"]), ops._p(params.bn2g),
+                      ops._p(tape["ms"]), ops._p(tape["ss"]), ops._p(params.bnsg), C, ops._p(grads.bn2g), ops._p(grads.bn2b),
+                      ops._p(grads.bnsg), ops._p(grads.bnsb), ops._p(loss), ops._stream())
     elif C % 64 == 0:
         dc2 = arena.get(tag + ".dc2", tuple(c2.shape))
         dsc = arena.get(tag + ".dsc", tuple(sc.shape))
-        rc = lib.mft_bn_backward2(ops._p(c2), ops._p(sc), C, ops._p(d_out), C, ops._p(dc2), ops._p(dsc), C, C, rows, groups,
-                                  ops._p(tape["m2"]), ops._p(tape["s2"]), ops._p(params.bn2g), ops._p(tape["ms"]),
-                                  ops._p(tape["ss"]), ops._p(params.bnsg), C, ops._p(grads.bn2g), ops._p(grads.bn2b),
-                                  ops._p(grads.bnsg), ops._p(grads.bnsb), ops._stream())
-        ops._lib.check(rc, "mft_bn_backward2")
+        ops._lib.call("mft_bn_backward2", ops._p(c2), ops._p(sc), C, ops._p(d_out), C, ops._p(dc2), ops._p(dsc), C, C, rows, groups,
+                      ops._p(tape["m2"]), ops._p(tape["s2"]), ops._p(params.bn2g), ops._p(tape["ms"]), ops._p(tape["ss"]),
+                      ops._p(params.bnsg), C, ops._p(grads.bn2g), ops._p(grads.bn2b), ops._p(grads.bnsg), ops._p(grads.bnsb),
+                      ops._stream())
     else:
         dc2 = bn_bwd(c2, d_out, tape["m2"], tape["s2"], params.bn2g, grads.bn2g, grads.bn2b, None, "dc2")
         dsc = bn_bwd(sc, d_out, tape["ms"], tape["ss"], params.bnsg, grads.bnsg, grads.bnsb, None, "dsc")
@@ -772,10 +751,9 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
         dc1 = arena.get(tag + ".dc1", tuple(c1.shape))
         if ops.conv2d_wgrad_adam_dgrad(r1, dc2, w2, m_.c2w, v_.c2w, dxp, 1 if hyper is not None else step, ipg, lr=lr,
                                        hyper=hyper):
-            ops._lib.check(lib.mft_col2im_bn_backward_small(ops._p(dxp), ops._p(c1), ops._p(r1), ops._p(dc1), n, oh, ow, C, ipg,
-                                                            ops._p(tape["m1"]), ops._p(tape["s1"]), ops._p(params.bn1g), C,
-                                                            ops._p(grads.bn1g), ops._p(grads.bn1b), ops._stream()),
-                           "mft_col2im_bn_backward_small")
+            ops._lib.call("mft_col2im_bn_backward_small", ops._p(dxp), ops._p(c1), ops._p(r1), ops._p(dc1), n, oh, ow, C, ipg,
+                          ops._p(tape["m1"]), ops._p(tape["s1"]), ops._p(params.bn1g), C, ops._p(grads.bn1g), ops._p(grads.bn1b),
+                          ops._stream())
             done_c2 = True
     def adam_tail():
         m, v, step, lr = adam
@@ -798,7 +776,7 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
         m_, v_, step, lr = adam
         hyper = step if torch.is_tensor(step) else None
         st = 1 if hyper is not None else step
-        dc1 = _dgrad_c2_bn1(lib, tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd)
+        dc1 = _dgrad_c2_bn1(tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd)
         adam_tail()
         kw = dict(lr=lr, hyper=hyper)
         fw = x_next is not None
@@ -824,7 +802,7 @@ def last_block_backward(tape, dfeat, params, grads, arena, ipg, tag="bw", adam=N
             tn["x"] = x_next
         return
     if not done_c2:
-        dc1 = _dgrad_c2_bn1(lib, tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd)
+        dc1 = _dgrad_c2_bn1(tape, params, grads, arena, tag, dc2, c1, r1, n, oh, ow, C, ipg, bn_bwd)
         wgrad(r1, dc2, "c2w", 3, 1, 1)
     wgrad(x, dc1, "c1w", 3, 2, 1)
     wgrad(x, dsc, "scw", 1, 2, 0)
@@ -967,18 +945,16 @@ def wcompute(G, name, x, F, n_graphs, N, n_groups, arena, tag="wc"):
         outs = [hbuf[0], hbuf[1], hbuf[0], hbuf[2]]                   # h1 -> h2 -> h3 (over h1) -> h4
         h_in, ld_in, K, Kpad = xin, ld, F, Kp
         for li, (w, b, gam, beta, cout) in enumerate(layers):
-            ops._lib.check(lib.mft_pair_mlp_layer(ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij),
-                                                  ops._p(scale[li - 1]) if li else None, ops._p(shift[li - 1]) if li else None,
-                                                  ops._p(w), K, Kpad, ops._p(b), ops._p(outs[li]), cout, ng, gpg, N,
-                                                  ops.LRELU_SLOPE, ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n), 1 if PAIR_F16X2 else 0, st()),
-                           "mft_pair_mlp_layer")
-            ops._lib.check(lib.mft_pair_mlp_stats_finalize(ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n), ng, tiles_m, cout,
-                                                           ops._p(gam), ops._p(beta), ops.BN_EPS, ops._p(scale[li]),
-                                                           ops._p(shift[li]), None, None, st()), "mft_pair_mlp_stats_finalize")
+            ops._lib.call("mft_pair_mlp_layer", ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij),
+                          ops._p(scale[li - 1]) if li else None, ops._p(shift[li - 1]) if li else None, ops._p(w), K, Kpad, ops._p(b),
+                          ops._p(outs[li]), cout, ng, gpg, N, ops.LRELU_SLOPE, ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n),
+                          1 if PAIR_F16X2 else 0, st())
+            ops._lib.call("mft_pair_mlp_stats_finalize", ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n), ng, tiles_m, cout, ops._p(gam),
+                          ops._p(beta), ops.BN_EPS, ops._p(scale[li]), ops._p(shift[li]), None, None, st())
             h_in, ld_in, K, Kpad = outs[li], cout, cout, cout
-        ops._lib.check(lib.mft_pair_mlp_score(ops._p(h_in), widths[3], ops._p(scale[3]), ops._p(shift[3]), ops._p(w5), ops._p(b5),
-                                              ops.LRELU_SLOPE, ops._p(s_ut), ng, gpg, N, st()), "mft_pair_mlp_score")
-        ops._lib.check(lib.mft_masked_softmax_ut(ops._p(s_ut), ops._p(A[g0 * gpg:]), ng * gpg, N, st()), "mft_masked_softmax_ut")
+        ops._lib.call("mft_pair_mlp_score", ops._p(h_in), widths[3], ops._p(scale[3]), ops._p(shift[3]), ops._p(w5), ops._p(b5),
+                      ops.LRELU_SLOPE, ops._p(s_ut), ng, gpg, N, st())
+        ops._lib.call("mft_masked_softmax_ut", ops._p(s_ut), ops._p(A[g0 * gpg:]), ng * gpg, N, st())
     return A
 
 
@@ -989,10 +965,8 @@ def wcompute_unfused(G, name, x, F, n_graphs, N, n_groups, arena, tag="wc"):
     Kp = ops.round_up(F, 32)
     rows = n_graphs * N * N
     rpg = rows // n_groups
-    lib = ops._lib.lib()
     d = arena.get(tag + ".d", (rows, Kp))
-    ops._lib.check(lib.mft_pair_absdiff(ops._p(x), x.shape[1], ops._p(d), Kp, n_graphs, N, F, ops._stream()),
-                   "mft_pair_absdiff")
+    ops._lib.call("mft_pair_absdiff", ops._p(x), x.shape[1], ops._p(d), Kp, n_graphs, N, F, ops._stream())
     h, K = d, Kp
     for li, (w, b, g, beta, cout) in enumerate(layers):
         o = ops.gemm(h, K, w, cout, bias=b, out=arena.get(tag + ".h%d" % li, (rows, cout)))
@@ -1001,7 +975,7 @@ def wcompute_unfused(G, name, x, F, n_graphs, N, n_groups, arena, tag="wc"):
         h, K = o, cout
     sc = ops.gemm(h, K, w5, 1, bias=b5, out=arena.get(tag + ".s", (rows, 1)))
     A = arena.get(tag + ".A", (n_graphs, N, N))
-    ops._lib.check(lib.mft_masked_softmax(ops._p(sc), 1, ops._p(A), n_graphs, N, ops._stream()), "mft_masked_softmax")
+    ops._lib.call("mft_masked_softmax", ops._p(sc), 1, ops._p(A), n_graphs, N, ops._stream())
     return A
 
 
@@ -1011,8 +985,7 @@ def gconv(G, name, A, x, F, n_graphs, N, n_groups, arena, tag="gc"):
     rows = n_graphs * N
     ldy = ops.round_up(2 * F, 32)
     y = arena.get(tag + ".y", (rows, ldy))
-    ops._lib.check(ops._lib.lib().mft_graph_aggregate(ops._p(A), ops._p(x), x.shape[1], ops._p(y), ldy, n_graphs, N, F,
-                                                      ops._stream()), "mft_graph_aggregate")
+    ops._lib.call("mft_graph_aggregate", ops._p(A), ops._p(x), x.shape[1], ops._p(y), ldy, n_graphs, N, F, ops._stream())
     o = ops.gemm(y, ldy, w, cout, bias=b, out=arena.get(tag + ".o", (rows, cout)))
     if g is not None:
         rpg = rows // n_groups
@@ -1046,8 +1019,7 @@ def gnnnet_scores(G, feats, n_episodes, n_way, n_support, n_query, arena, fold=F
     N = n_way * (n_support + 1)
     n_graphs = n_episodes * n_query
     nodes = arena.get(tag + ".nodes", (n_graphs * N, 256))
-    ops._lib.check(ops._lib.lib().mft_build_graph_nodes(ops._p(z), 128, ops._p(nodes), 256, n_episodes, n_way,
-                                                        n_support, n_query, 1 if fold else 0, ops._stream()),
-                   "mft_build_graph_nodes")
+    ops._lib.call("mft_build_graph_nodes", ops._p(z), 128, ops._p(nodes), 256, n_episodes, n_way, n_support, n_query, 1 if fold else 0,
+                  ops._stream())
     out = gnn_forward(G, nodes, n_graphs, N, n_episodes, arena, tag + ".gnn")
     return ops.gather_query_scores(out, n_episodes, n_way, n_support, n_query)

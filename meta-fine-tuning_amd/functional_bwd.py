@@ -6,7 +6,6 @@ Covers what ``loss.backward()`` differentiates in MetaTemplate.train_loop2 / tra
 One episode per call as the reference's loops run it -- or k episodes in lockstep (``groups`` / ``episodes``: every BatchNorm keeps
 per-episode statistics, the parameter gradients are the sums over the k episodes); gradients come back in the reference's layouts.
 """
-import ctypes
 
 import torch
 
@@ -85,43 +84,31 @@ def bn_bwd(x2d, dy2d, C, rows, mean, rstd, gamma, y_act=None, act=NONE, need_dx=
     rpg = rows // groups
     ws = _empty((int(L.lib().mft_bn_backward_ws_floats(C, rpg, groups)),), dev)
     one = groups == 1                     # one group: its sums ARE the parameter gradients; several: summed by the finalize launch
-    rc = L.lib().mft_bn_backward_act(ops._p(x2d), x2d.shape[-1], ops._p(dy2d), dy2d.shape[-1], ops._p(y_act),
-                                     0 if y_act is None else y_act.shape[-1], ops._p(dx), 0 if dx is None else dx.shape[-1],
-                                     C, rpg, groups, ops._p(mean), ops._p(rstd), ops._p(gamma), 0, ops._p(dg) if one else None,
-                                     ops._p(db) if one else None, act, ops.LRELU_SLOPE, ops._p(ws), None if one else ops._p(dg),
-                                     None if one else ops._p(db), ops._p(dbias_zero), ops._stream())
-    L.check(rc, "mft_bn_backward_act")
+    L.call("mft_bn_backward_act", ops._p(x2d), x2d.shape[-1], ops._p(dy2d), dy2d.shape[-1], ops._p(y_act),
+           0 if y_act is None else y_act.shape[-1], ops._p(dx), 0 if dx is None else dx.shape[-1], C, rpg, groups, ops._p(mean),
+           ops._p(rstd), ops._p(gamma), 0, ops._p(dg) if one else None, ops._p(db) if one else None, act, ops.LRELU_SLOPE, ops._p(ws),
+           None if one else ops._p(dg), None if one else ops._p(db), ops._p(dbias_zero), ops._stream())
     return dx, dg, db
 
 
 def act_backward(dy, y, dx, C, act, accumulate, dy_off=0, y_off=0, dx_off=0):
     """dx[:, dx_off:dx_off+C] (+)= dy[:, dy_off:..] * act'(y[:, y_off:..]) on 2-D tensors with arbitrary row strides."""
     rows = dy.shape[0]
-    rc = L.lib().mft_act_backward(dy.data_ptr() + 4 * dy_off, dy.shape[1], y.data_ptr() + 4 * y_off, y.shape[1],
-                                  dx.data_ptr() + 4 * dx_off, dx.shape[1], C, rows, act, ops.LRELU_SLOPE,
-                                  1 if accumulate else 0, ops._stream())
-    L.check(rc, "mft_act_backward")
+    L.call("mft_act_backward", dy.data_ptr() + 4 * dy_off, dy.shape[1], y.data_ptr() + 4 * y_off, y.shape[1], dx.data_ptr() + 4 * dx_off,
+           dx.shape[1], C, rows, act, ops.LRELU_SLOPE, 1 if accumulate else 0, ops._stream())
 
 
 def colsum(x2d, C):
     rows = x2d.shape[0]
     out = _empty((C,), x2d.device)
     ws = _empty((((rows + 255) // 256) * C,), x2d.device)
-    L.check(L.lib().mft_colsum(ops._p(x2d), x2d.shape[1], C, rows, ops._p(out), ops._p(ws), ops._stream()), "mft_colsum")
+    L.call("mft_colsum", ops._p(x2d), x2d.shape[1], C, rows, ops._p(out), ops._p(ws), ops._stream())
     return out
 
 
 # =========================================================================================== feature-wise transformation
 
-class _FwtJob(ctypes.Structure):
-    """MftFwtJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("w", "b", "gamma", "beta", "w_fold", "b_fold", "gm")] + [("C", ctypes.c_int), ("col", ctypes.c_int)]
-
-
-class _FwtGradJob(ctypes.Structure):
-    """MftFwtGradJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("w", "b", "gamma", "beta", "gm", "dw_fold", "db_fold", "dw", "db", "dgamma", "dbeta")] + \
-               [("C", ctypes.c_int), ("col", ctypes.c_int)]
+_FwtJob, _FwtGradJob = L.struct("MftFwtJob"), L.struct("MftFwtGradJob")
 
 
 class FwtState:
@@ -154,8 +141,8 @@ class FwtState:
             a.w_fold, a.b_fold, a.gm, a.C, a.col = wf.data_ptr(), bf.data_ptr(), gm.data_ptr(), C, col
             off += n
         self.tot = tot
-        L.check(L.lib().mft_fwt_draw_fold(arr, len(self.layers), self.groups, self.ld, int(seed) & 0xFFFFFFFFFFFFFFFF, ops._p(index),
-                                          ops._p(noise_in), ops._p(self.noise), ops._p(self.words), ops._stream()), "mft_fwt_draw_fold")
+        L.call("mft_fwt_draw_fold", arr, len(self.layers), self.groups, self.ld, int(seed) & 0xFFFFFFFFFFFFFFFF, ops._p(index),
+               ops._p(noise_in), ops._p(self.noise), ops._p(self.words), ops._stream())
         self.dfold = None
 
     def grad_slots(self, name):
@@ -180,7 +167,7 @@ class FwtState:
                 dg, dbt = _empty((1, C, 1, 1), dev), _empty((1, C, 1, 1), dev)
                 a.dgamma, a.dbeta = dg.data_ptr(), dbt.data_ptr()
                 grads[name + ".gamma"], grads[name + ".beta"] = dg, dbt
-        L.check(L.lib().mft_fwt_unfold(arr, len(self.layers), self.groups, self.ld, ops._p(self.noise), ops._stream()), "mft_fwt_unfold")
+        L.call("mft_fwt_unfold", arr, len(self.layers), self.groups, self.ld, ops._p(self.noise), ops._stream())
 
 
 def bn_bwd_per_group(x2d, dy2d, C, rows, mean, rstd, gamma_g, dg_g, db_g, y_act=None, act=NONE, groups=1):
@@ -190,11 +177,9 @@ def bn_bwd_per_group(x2d, dy2d, C, rows, mean, rstd, gamma_g, dg_g, db_g, y_act=
     dx = _empty(x2d.shape, dev)
     rpg = rows // groups
     ws = _empty((int(L.lib().mft_bn_backward_ws_floats(C, rpg, groups)),), dev)
-    rc = L.lib().mft_bn_backward_act(ops._p(x2d), x2d.shape[-1], ops._p(dy2d), dy2d.shape[-1], ops._p(y_act),
-                                     0 if y_act is None else y_act.shape[-1], ops._p(dx), dx.shape[-1], C, rpg, groups, ops._p(mean),
-                                     ops._p(rstd), ops._p(gamma_g), C, ops._p(dg_g), ops._p(db_g), act, ops.LRELU_SLOPE, ops._p(ws),
-                                     None, None, None, ops._stream())
-    L.check(rc, "mft_bn_backward_act")
+    L.call("mft_bn_backward_act", ops._p(x2d), x2d.shape[-1], ops._p(dy2d), dy2d.shape[-1], ops._p(y_act),
+           0 if y_act is None else y_act.shape[-1], ops._p(dx), dx.shape[-1], C, rpg, groups, ops._p(mean), ops._p(rstd), ops._p(gamma_g),
+           C, ops._p(dg_g), ops._p(db_g), act, ops.LRELU_SLOPE, ops._p(ws), None, None, None, ops._stream())
     return dx
 
 
@@ -232,8 +217,8 @@ def resnet10_forward_taped(W, x, running=None, groups=1, fwt=None):
     PH = (H0 + 2 - 3) // 2 + 1
     a0 = _empty((n, PH, PH, 64), dev)
     arg = torch.empty((n, PH, PH, 64), device=dev, dtype=torch.uint8)
-    L.check(L.lib().mft_bn_relu_maxpool_arg(ops._p(c0), ops._p(a0), ops._p(arg), n, H0, H0, 64, n // groups, ops._p(m0), ops._p(s0),
-                                            ops._p(g0), ops._p(b0), ops._stream()), "mft_bn_relu_maxpool_arg")
+    L.call("mft_bn_relu_maxpool_arg", ops._p(c0), ops._p(a0), ops._p(arg), n, H0, H0, 64, n // groups, ops._p(m0), ops._p(s0), ops._p(g0),
+           ops._p(b0), ops._stream())
     t.update(c0=c0, m0=m0, s0=s0, a0=a0, arg=arg)
     a = a0
     blocks = []
@@ -380,8 +365,7 @@ def resnet10_backward(W, t, dfeat, need, act_grads=None):
     c0, a0 = t["c0"], t["a0"]
     H0 = c0.shape[1]
     d_bn0 = _empty(c0.shape, dev)
-    L.check(L.lib().mft_maxpool_relu_backward(ops._p(d_out), ops._p(t["arg"]), ops._p(a0), ops._p(d_bn0), n, H0, H0, 64,
-                                              ops._stream()), "mft_maxpool_relu_backward")
+    L.call("mft_maxpool_relu_backward", ops._p(d_out), ops._p(t["arg"]), ops._p(a0), ops._p(d_bn0), n, H0, H0, 64, ops._stream())
     g0 = W.bn["trunk.1"][0]
     dc0, dg, db = bn_bwd(c0.view(-1, 64), d_bn0.view(-1, 64), 64, n * H0 * H0, t["m0"], t["s0"], g0, groups=groups)
     grads["trunk.1.weight"], grads["trunk.1.bias"] = dg, db
@@ -491,23 +475,23 @@ def wcompute_taped(G, name, x, F, n_graphs, N, groups=1):
         z = _empty((rows, cout), dev)
         sc, sh, m, s = (_empty((groups, cout), dev) for _ in range(4))
         if rk:
-            L.check(lib.mft_pair_mlp_layer_rk(ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij), ops._p(sc_prev), ops._p(sh_prev), ops._p(w),
-                                              K, Kpad, ops._p(b), ops._p(z), cout, groups, gpg, N, ops.LRELU_SLOPE, ops._p(ws_mean),
-                                              ops._p(ws_m2), ops._p(ws_n), ops._stream()), "mft_pair_mlp_layer_rk")
+            L.call("mft_pair_mlp_layer_rk", ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij), ops._p(sc_prev), ops._p(sh_prev),
+                   ops._p(w), K, Kpad, ops._p(b), ops._p(z), cout, groups, gpg, N, ops.LRELU_SLOPE, ops._p(ws_mean), ops._p(ws_m2),
+                   ops._p(ws_n), ops._stream())
         else:
-            L.check(lib.mft_pair_mlp_layer(ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij), ops._p(sc_prev), ops._p(sh_prev), ops._p(w),
-                                           K, Kpad, ops._p(b), ops._p(z), cout, groups, gpg, N, ops.LRELU_SLOPE, ops._p(ws_mean),
-                                           ops._p(ws_m2), ops._p(ws_n), 1 if Fn.PAIR_F16X2 else 0, ops._stream()), "mft_pair_mlp_layer")
-        L.check((lib.mft_pair_mlp_stats_finalize_rk if rk else lib.mft_pair_mlp_stats_finalize)(
-            ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n), groups, tiles_m, cout, ops._p(gam), ops._p(beta), ops.BN_EPS, ops._p(sc),
-            ops._p(sh), ops._p(m), ops._p(s), ops._stream()), "mft_pair_mlp_stats_finalize")
+            L.call("mft_pair_mlp_layer", ops._p(h_in), ld_in, 0 if li == 0 else 1, ops._p(ij), ops._p(sc_prev), ops._p(sh_prev), ops._p(w),
+                   K, Kpad, ops._p(b), ops._p(z), cout, groups, gpg, N, ops.LRELU_SLOPE, ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n),
+                   1 if Fn.PAIR_F16X2 else 0, ops._stream())
+        L.call("mft_pair_mlp_stats_finalize_rk" if rk else "mft_pair_mlp_stats_finalize",
+               ops._p(ws_mean), ops._p(ws_m2), ops._p(ws_n), groups, tiles_m, cout, ops._p(gam), ops._p(beta), ops.BN_EPS, ops._p(sc),
+               ops._p(sh), ops._p(m), ops._p(s), ops._stream())
         t["z"].append(z); t["bn"].append((sc, sh, m, s))
         h_in, ld_in, K, Kpad, sc_prev, sh_prev = z, cout, cout, cout, sc, sh
     s_ut = _empty((rows,), dev)
-    L.check(lib.mft_pair_mlp_score(ops._p(h_in), layers[3][4], ops._p(sc_prev), ops._p(sh_prev), ops._p(w5), ops._p(b5), ops.LRELU_SLOPE,
-                                   ops._p(s_ut), groups, gpg, N, ops._stream()), "mft_pair_mlp_score")
+    L.call("mft_pair_mlp_score", ops._p(h_in), layers[3][4], ops._p(sc_prev), ops._p(sh_prev), ops._p(w5), ops._p(b5), ops.LRELU_SLOPE,
+           ops._p(s_ut), groups, gpg, N, ops._stream())
     A = _empty((n_graphs, N, N), dev)
-    L.check(lib.mft_masked_softmax_ut(ops._p(s_ut), ops._p(A), n_graphs, N, ops._stream()), "mft_masked_softmax_ut")
+    L.call("mft_masked_softmax_ut", ops._p(s_ut), ops._p(A), n_graphs, N, ops._stream())
     t["A"] = A
     return A, t
 
@@ -555,8 +539,8 @@ def wcompute_backward(G, t, dA, x, dX, n_graphs, N, grads, prefix, wb=None):
     ds = t["lease"].take((rows, 32), dev)              # column 0: gradient of the compact symmetric score (columns 1..31 stay 0)
     rd = _empty((n_graphs * N,), dev)
     db5 = _empty((1,), dev)                    # conv2d_last.bias shifts every logit of a softmax row alike: zero gradient, from this launch
-    L.check(lib.mft_pair_softmax_ut_backward(ops._p(t["A"]), ops._p(dA), ops._p(ij), ops._p(rd), ops._p(ds), 32, n_graphs, N,
-                                             ops._p(db5), ops._stream()), "mft_pair_softmax_ut_backward")
+    L.call("mft_pair_softmax_ut_backward", ops._p(t["A"]), ops._p(dA), ops._p(ij), ops._p(rd), ops._p(ds), 32, n_graphs, N, ops._p(db5),
+           ops._stream())
     h4 = _pair_activation(t, 3, layers, rows)
     dh, dW, _ = _linear_bwd(h4, 96, w5, ds, 1, db=db5, wb=wb)
     del h4
@@ -571,10 +555,9 @@ def wcompute_backward(G, t, dA, x, dX, n_graphs, N, grads, prefix, wb=None):
         dz = _empty((rows, cout), dev)
         # (dbz: the 1x1 convolution's bias sits in front of the BatchNorm -- its gradient is identically zero and comes back as zeros
         # from this launch; round 5 spent two column-sum launches per layer on the rounding noise of sum(dz))
-        L.check(lib.mft_pair_bn_act_backward(ops._p(dh), dh.shape[1], ops._p(z), cout, ops._p(sc), ops._p(sh), ops._p(m), ops._p(s),
-                                             ops._p(gam), ops._p(ij), N, rows // groups, groups, n_tot, ops.LRELU_SLOPE, ops._p(ws),
-                                             ops._p(sums), ops._p(dpar), ops._p(dbz), ops._p(dz), ops._stream()),
-                "mft_pair_bn_act_backward")
+        L.call("mft_pair_bn_act_backward", ops._p(dh), dh.shape[1], ops._p(z), cout, ops._p(sc), ops._p(sh), ops._p(m), ops._p(s),
+               ops._p(gam), ops._p(ij), N, rows // groups, groups, n_tot, ops.LRELU_SLOPE, ops._p(ws), ops._p(sums), ops._p(dpar),
+               ops._p(dbz), ops._p(dz), ops._stream())
         grads[prefix + ".bn_%d.weight" % (li + 1)], grads[prefix + ".bn_%d.bias" % (li + 1)] = dpar[cout:], dpar[:cout]      # (views of this layer's own buffer)
         grads[prefix + ".conv2d_%d.bias" % (li + 1)] = dbz
         if li > 0:
@@ -590,8 +573,7 @@ def wcompute_backward(G, t, dA, x, dX, n_graphs, N, grads, prefix, wb=None):
             for r0 in range(0, rows, PAIR_CHUNK_ROWS):
                 nr = min(PAIR_CHUNK_ROWS, rows - r0)
                 d = _empty((nr, Kp), dev)
-                L.check(lib.mft_pair_absdiff_ut(ops._p(x), x.shape[1], ops._p(ij), ops._p(d), Kp, F, N, r0, nr, ops._stream()),
-                        "mft_pair_absdiff_ut")
+                L.call("mft_pair_absdiff_ut", ops._p(x), x.shape[1], ops._p(ij), ops._p(d), Kp, F, N, r0, nr, ops._stream())
                 dzc = dz[r0:r0 + nr]
                 wg = ops.conv2d_wgrad_oihw if wb is None else wb.add
                 part = wg(d.view(nr, 1, 1, Kp), dzc.view(nr, 1, 1, cout), cout, 1, 1, 1, 0, cin_valid=F).view(cout, F)
@@ -602,8 +584,8 @@ def wcompute_backward(G, t, dA, x, dX, n_graphs, N, grads, prefix, wb=None):
                 else:                                    # ... once the deferred launch has produced both
                     wb.then(lambda part=part, dW=dW: act_backward(part, part, dW, F, NONE, True))
                 dd = _linear_dgrad(dzc, w, Kp)
-                L.check(lib.mft_pair_dx_gather(ops._p(x), x.shape[1], ops._p(dd), Kp, ops._p(dX), dX.shape[1], n_graphs, N, F, r0, nr,
-                                               ops._stream()), "mft_pair_dx_gather")
+                L.call("mft_pair_dx_gather", ops._p(x), x.shape[1], ops._p(dd), Kp, ops._p(dX), dX.shape[1], n_graphs, N, F, r0, nr,
+                       ops._stream())
             grads[prefix + ".conv2d_1.weight"] = dW.view(cout, F, 1, 1)
 
 
@@ -648,9 +630,8 @@ def gconv_backward(G, t, d_o, x, dX, n_graphs, N, grads, prefix, first=False, wb
     grads[prefix + ".fc.weight"] = dW
     grads[prefix + ".fc.bias"] = db
     dA = _empty((n_graphs, N, N), x.device)
-    L.check(L.lib().mft_graph_aggregate_backward(ops._p(t["A"]), ops._p(x), x.shape[1], ops._p(dy), dy.shape[1],
-                                                 ops._p(dX), dX.shape[1], ops._p(dA), n_graphs, N, F, 0 if first else 1, ops._stream()),
-            "mft_graph_aggregate_backward")
+    L.call("mft_graph_aggregate_backward", ops._p(t["A"]), ops._p(x), x.shape[1], ops._p(dy), dy.shape[1], ops._p(dX), dX.shape[1],
+           ops._p(dA), n_graphs, N, F, 0 if first else 1, ops._stream())
     return dA
 
 
@@ -703,8 +684,8 @@ def head_backward(G, t, dscores):
     dX = _empty((rows, 256), dev)              # first written (all 229 feature columns) by layer_last's aggregate backward: no zero fill
     d_out = _empty((rows, 32), dev)
     db_last = _empty((n_way,), dev)            # layer_last.fc.bias: the column sums of dscores, from the same launch
-    L.check(L.lib().mft_gather_query_scores_backward(ops._p(dscores.contiguous()), ops._p(d_out), d_out.shape[1], k, n_way, ns, nq,
-                                                     ops._p(db_last), ops._stream()), "mft_gather_query_scores_backward")
+    L.call("mft_gather_query_scores_backward", ops._p(dscores.contiguous()), ops._p(d_out), d_out.shape[1], k, n_way, ns, nq,
+           ops._p(db_last), ops._stream())
     wb = ops.WgradBatch(WGRAD_BATCH)            # the head's 16 weight gradients: registered as the pass goes, run together at its end
     if WGRAD_BATCH:
         pair_activations(G, t["wc"], n_graphs * (N * (N + 1) // 2))
@@ -718,8 +699,7 @@ def head_backward(G, t, dscores):
         wcompute_backward(G, t["wc"][i], dA, x, dX, n_graphs, N, grads, "gnn.layer_w%d" % i, wb=wb)
     per = n_way * ((2 * ns if fold else ns) + nq)
     dz = _empty((k * per, 128), dev)
-    L.check(L.lib().mft_build_graph_nodes_backward(ops._p(dX), 256, ops._p(dz), 128, k, n_way, ns, nq, 1 if fold else 0,
-                                                   ops._stream()), "mft_build_graph_nodes_backward")
+    L.call("mft_build_graph_nodes_backward", ops._p(dX), 256, ops._p(dz), 128, k, n_way, ns, nq, 1 if fold else 0, ops._stream())
     dbz = _empty((128,), dev)                  # fc.0.bias sits in front of fc.1 (BatchNorm1d): zero gradient, from its backward launch
     dzr, dg, db = bn_bwd(t["z_raw"], dz, 128, k * per, t["mz"], t["sz"], G.fc_g, groups=k, dbias_zero=dbz)
     grads["fc.1.weight"], grads["fc.1.bias"] = dg, db

@@ -258,10 +258,8 @@ def linear_head_adapt(z_support, y_support, z_query, w, b, n_way, n_support, epo
     W = w.detach().clone().float().contiguous().view(1, n_way, K)
     bias = b.detach().clone().float().contiguous().view(1, n_way)
     y_dev = torch.from_numpy(np.asarray(y_support).astype(np.int32)).to(dev)
-    rc = ops._lib.lib().mft_linear_head_sgd_run(ops._p(z_support.contiguous()), ops._p(y_dev), ops._p(table), 1, support_size, K,
-                                                n_way, table.shape[0], batch_size, ops._p(W), ops._p(bias), 0.01, 0.9, 0.9, 0.001,
-                                                ops._stream())
-    ops._lib.check(rc, "mft_linear_head_sgd_run")
+    ops._lib.call("mft_linear_head_sgd_run", ops._p(z_support.contiguous()), ops._p(y_dev), ops._p(table), 1, support_size, K, n_way,
+                  table.shape[0], batch_size, ops._p(W), ops._p(bias), 0.01, 0.9, 0.9, 0.001, ops._stream())
     wpad = torch.zeros((32, K), device=dev)               # rows >= n_way stay zero (N padded to the 32-wide tile)
     wpad[:n_way] = W[0]
     return ops.gemm(z_query, K, wpad[:n_way].contiguous(), n_way, bias=bias[0].contiguous())
@@ -293,10 +291,8 @@ def linear_head_adapt_episodes(z_support, y_support, z_query, w0, b0, n_way, n_s
     y_dev = torch.from_numpy(y).to(dev)
     W = w0.detach().to(dev, torch.float32).reshape(E, n_way, D).clone()
     bias = b0.detach().to(dev, torch.float32).reshape(E, n_way).clone()
-    rc = ops._lib.lib().mft_linear_head_sgd_run(ops._p(z_support.contiguous().float()), ops._p(y_dev), ops._p(table), E, S, D, n_way,
-                                                table.shape[1], table.shape[2], ops._p(W), ops._p(bias), 0.01, 0.9, 0.9, 0.001,
-                                                ops._stream())
-    ops._lib.check(rc, "mft_linear_head_sgd_run")
+    ops._lib.call("mft_linear_head_sgd_run", ops._p(z_support.contiguous().float()), ops._p(y_dev), ops._p(table), E, S, D, n_way,
+                  table.shape[1], table.shape[2], ops._p(W), ops._p(bias), 0.01, 0.9, 0.9, 0.001, ops._stream())
     zq = z_query.contiguous().float().view(E * Q, D)
     scores = ops.gemm(zq, D, W if E > 1 else W[0], n_way, rows_per_group=Q if E > 1 else 0)
     scores.view(E, Q, n_way).add_(bias.view(E, 1, n_way))

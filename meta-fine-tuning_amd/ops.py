@@ -66,7 +66,7 @@ def nchw_to_nhwc(x):
     _f32c(x)
     n, C, H, W = x.shape
     y = torch.empty((n, H, W, C), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_nchw_to_nhwc(_p(x), _p(y), n, C, H, W, _stream()), "mft_nchw_to_nhwc")
+    _lib.call("mft_nchw_to_nhwc", _p(x), _p(y), n, C, H, W, _stream())
     return y
 
 
@@ -85,7 +85,7 @@ def pack_conv_weight(w, rows32=False):
         pk.rows32 = buf
     else:
         pk = torch.empty((Cout, kpad), device=w.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_pack_oihw(_p(w), _p(pk), Cout, Cin, KH, KW, kpad, _stream()), "mft_pack_oihw")
+    _lib.call("mft_pack_oihw", _p(w), _p(pk), Cout, Cin, KH, KW, kpad, _stream())
     return pk
 
 
@@ -126,7 +126,7 @@ class PackPlan:
         if self.table is None:
             import numpy as np
             self.table = torch.from_numpy(np.asarray(self.jobs, dtype=np.int64)).to(self.keep[0][1].device)
-        _lib.check(_lib.lib().mft_pack_oihw_multi(_p(self.table), len(self.jobs), self.total, _stream()), "mft_pack_oihw_multi")
+        _lib.call("mft_pack_oihw_multi", _p(self.table), len(self.jobs), self.total, _stream())
 
 
 class SplitPlan:
@@ -163,11 +163,11 @@ class SplitPlan:
             j = list(self.jobs[only])
             j[7] = 0
             tab = torch.from_numpy(np.asarray([j], dtype=np.int64)).to(self.keep[only][0].device)
-            _lib.check(_lib.lib().mft_split_bf16x3_multi(_p(tab), 1, j[2], _stream()), "mft_split_bf16x3_multi")
+            _lib.call("mft_split_bf16x3_multi", _p(tab), 1, j[2], _stream())
             return
         if self.table is None:
             self.table = torch.from_numpy(np.asarray(self.jobs, dtype=np.int64)).to(self.keep[0][0].device)
-        _lib.check(_lib.lib().mft_split_bf16x3_multi(_p(self.table), len(self.jobs), self.total, _stream()), "mft_split_bf16x3_multi")
+        _lib.call("mft_split_bf16x3_multi", _p(self.table), len(self.jobs), self.total, _stream())
 
     def run(self):
         if self.jobs:
@@ -177,7 +177,7 @@ class SplitPlan:
 def unpack_conv_weight(pk, shape):
     Cout, Cin, KH, KW = shape
     w = torch.empty(shape, device=pk.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_unpack_oihw(_p(pk), _p(w), Cout, Cin, KH, KW, pk.shape[-1], _stream()), "mft_unpack_oihw")
+    _lib.call("mft_unpack_oihw", _p(pk), _p(w), Cout, Cin, KH, KW, pk.shape[-1], _stream())
     return w
 
 
@@ -186,8 +186,7 @@ def pack_dgrad_weight(w_pk, Cout, Cin, KH, KW, groups=1):
     w_pk = _f32c(w_pk)
     K = KH * KW * Cin
     wt = torch.empty((groups, Cin, KH * KW * Cout), device=w_pk.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_pack_dgrad(_p(w_pk), _p(wt), Cout, Cin, KH, KW, groups, Cout * K, Cin * KH * KW * Cout,
-                                         _stream()), "mft_pack_dgrad")
+    _lib.call("mft_pack_dgrad", _p(w_pk), _p(wt), Cout, Cin, KH, KW, groups, Cout * K, Cin * KH * KW * Cout, _stream())
     return wt
 
 
@@ -211,9 +210,8 @@ def conv2d(x, w_pk, Cout, KH, KW, stride, pad, imgs_per_group=0, bias=None, out=
         nws = _ksplit_ws(n * OH * OW, Cout, w_pk.shape[-1])
         if nws:
             ws = torch.empty((nws,), device=x.device, dtype=torch.float32)
-            rc = _lib.lib().mft_conv2d_nhwc_ksplit(_p(x), Cin, _p(w_pk), _p(bias), _p(out), Cout, n, H, W, Cin, Cout, KH, KW,
-                                                   stride, pad, _p(ws), _stream())
-            _lib.check(rc, "mft_conv2d_nhwc_ksplit")
+            _lib.call("mft_conv2d_nhwc_ksplit", _p(x), Cin, _p(w_pk), _p(bias), _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad,
+                      _p(ws), _stream())
             return out
     if w_pk.dim() == 3 and 1 < w_pk.shape[0] <= SMALL_GROUPS and bias is None and Cin != 3:
         # a few episodes in lockstep: grid.y = episode on the K-sliced implicit GEMM (the weight-streaming kernels need >= 16
@@ -222,13 +220,11 @@ def conv2d(x, w_pk, Cout, KH, KW, stride, pad, imgs_per_group=0, bias=None, out=
         nws = _ksplit_ws(imgs_per_group * OH * OW, Cout, w_pk.shape[-1], G)
         if nws:
             ws = torch.empty((nws,), device=x.device, dtype=torch.float32)
-            rc = _lib.lib().mft_conv2d_nhwc_ksplit_grouped(_p(x), Cin, _p(w_pk), _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad,
-                                                           imgs_per_group, wgs, _p(ws), _stream())
-            _lib.check(rc, "mft_conv2d_nhwc_ksplit_grouped")
+            _lib.call("mft_conv2d_nhwc_ksplit_grouped", _p(x), Cin, _p(w_pk), _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad,
+                      imgs_per_group, wgs, _p(ws), _stream())
             return out
-    rc = _lib.lib().mft_conv2d_nhwc(_p(x), Cin, _p(w_pk), _p(bias), _p(out), Cout, n, H, W, Cin, Cout, KH, KW,
-                                    stride, pad, imgs_per_group, wgs, _stream())
-    _lib.check(rc, "mft_conv2d_nhwc")
+    _lib.call("mft_conv2d_nhwc", _p(x), Cin, _p(w_pk), _p(bias), _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad, imgs_per_group,
+              wgs, _stream())
     return out
 
 
@@ -250,7 +246,7 @@ def split_weight_x3(w_pk):
     """packed fp32 weights [Cout, Kpad] -> three bf16 planes [3, Cout, Kpad] (int16 storage) for conv2d_x3."""
     _f32c(w_pk)
     planes = torch.empty((3,) + tuple(w_pk.shape), device=w_pk.device, dtype=torch.int16)
-    _lib.check(_lib.lib().mft_split_bf16x3(_p(w_pk), _p(planes), w_pk.numel(), _stream()), "mft_split_bf16x3")
+    _lib.call("mft_split_bf16x3", _p(w_pk), _p(planes), w_pk.numel(), _stream())
     return planes
 
 
@@ -259,15 +255,13 @@ def split_weight_h2(w_pk):
     (csrc/conv_x3.hip, "f16x2").  The conv2d_x3* wrappers below take either kind of planes and launch the matching kernels."""
     _f32c(w_pk)
     planes = torch.empty((2,) + tuple(w_pk.shape), device=w_pk.device, dtype=torch.int16)
-    _lib.check(_lib.lib().mft_split_f16x2(_p(w_pk), _p(planes), w_pk.numel(), _stream()), "mft_split_f16x2")
+    _lib.call("mft_split_f16x2", _p(w_pk), _p(planes), w_pk.numel(), _stream())
     return planes
 
 
 def _x3_fn(w3, stem):
     """The C entry point for these weight planes: three bf16 planes -> mft_conv2d_nhwc_x3*, two fp16 planes -> mft_conv2d_nhwc_h2*."""
-    kind = {3: "x3", 2: "h2"}[int(w3.shape[0])]
-    name = "mft_conv2d_nhwc_%s%s" % (kind, stem)
-    return getattr(_lib.lib(), name), name
+    return "mft_conv2d_nhwc_%s%s" % ({3: "x3", 2: "h2"}[int(w3.shape[0])], stem)
 
 
 def conv2d_x3(x, w3, Cout, KH, KW, stride, pad, out=None):
@@ -279,9 +273,8 @@ def conv2d_x3(x, w3, Cout, KH, KW, stride, pad, out=None):
     OW = (W + 2 * pad - KW) // stride + 1
     if out is None:
         out = torch.empty((n, OH, OW, Cout), device=x.device, dtype=torch.float32)
-    fn, name = _x3_fn(w3, "")
-    rc = fn(_p(x), Cin, _p(w3), w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad, _stream())
-    _lib.check(rc, name)
+    _lib.call(_x3_fn(w3, ""), _p(x), Cin, _p(w3), w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad,
+              _stream())
     return out
 
 
@@ -290,12 +283,9 @@ def conv2d_x3_bnstats(x, w3, Cout, KH, KW, stride, pad, imgs_per_group, out, ws,
     (computed from the output tiles while they are still in registers).  ``ws``: >= mft_conv2d_x3_stats_ws_floats floats."""
     _f32c(x)
     n, H, W, Cin = x.shape
-    fn, name = _x3_fn(w3, "_bnstats")
-    rc = fn(_p(x), Cin, _p(w3), w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout, KH, KW, stride, pad, imgs_per_group, eps,
-            _p(ws), _p(mean), _p(rstd), _stream())
-    if rc == _lib.MFT_EINVAL:
+    if not _lib.try_call(_x3_fn(w3, "_bnstats"), _p(x), Cin, _p(w3), w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout, KH, KW,
+                         stride, pad, imgs_per_group, eps, _p(ws), _p(mean), _p(rstd), _stream()):
         return None                       # outside the fused form's domain (e.g. an input of 2 GiB or more): caller uses conv + bn_stats
-    _lib.check(rc, name)
     return out, mean, rstd
 
 
@@ -306,12 +296,10 @@ def conv2d_x3_bnin_bnstats(c_raw, in_ws, in_gamma, in_beta, w3, Cout, imgs_per_g
     Returns None outside the kernel's domain."""
     _f32c(c_raw)
     n, H, W, Cin = c_raw.shape
-    fn, name = _x3_fn(w3, "_bnin_bnstats")
-    rc = fn(_p(c_raw), Cin, _p(in_ws), _p(in_gamma), _p(in_beta), _p(w3), w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout,
-            imgs_per_group, eps, _p(ws), _p(mean), _p(rstd), _stream())
-    if rc == _lib.MFT_EINVAL:
+    if not _lib.try_call(_x3_fn(w3, "_bnin_bnstats"), _p(c_raw), Cin, _p(in_ws), _p(in_gamma), _p(in_beta), _p(w3),
+                         w3.shape[1] * w3.shape[2], _p(out), Cout, n, H, W, Cin, Cout, imgs_per_group, eps, _p(ws), _p(mean), _p(rstd),
+                         _stream()):
         return None
-    _lib.check(rc, name)
     return out
 
 
@@ -323,10 +311,9 @@ def bn_apply_x3ws(x2d, C, rows_per_group, n_groups, ws, gamma, beta, out, act=AC
     _f32c(x2d)
     m, r = stats if stats is not None else (None, None)
     rm, rr = res_stats if res_stats is not None else (None, None)
-    rc = _lib.lib().mft_bn_apply_x3ws(_p(x2d), x2d.shape[-1], _p(out), out.shape[-1], C, rows_per_group, n_groups, _p(ws), _p(gamma),
-                                      _p(beta), _p(res), 0 if res is None else res.shape[-1], _p(res_ws), _p(res_gamma),
-                                      _p(res_beta), act, slope, eps, _p(m), _p(r), _p(rm), _p(rr), _stream())
-    _lib.check(rc, "mft_bn_apply_x3ws")
+    _lib.call("mft_bn_apply_x3ws", _p(x2d), x2d.shape[-1], _p(out), out.shape[-1], C, rows_per_group, n_groups, _p(ws), _p(gamma),
+              _p(beta), _p(res), 0 if res is None else res.shape[-1], _p(res_ws), _p(res_gamma), _p(res_beta), act, slope, eps, _p(m),
+              _p(r), _p(rm), _p(rr), _stream())
     return out
 
 
@@ -342,9 +329,7 @@ def gemm(a, K, w_pk, N, bias=None, out=None, ldo=None, rows_per_group=0):
     wgs = 0
     if w_pk.dim() == 3:
         wgs = w_pk.shape[1] * w_pk.shape[2]
-    rc = _lib.lib().mft_conv2d_nhwc(_p(a), lda, _p(w_pk), _p(bias), _p(out), ldo, M, 1, 1, K, N, 1, 1, 1, 0,
-                                    rows_per_group, wgs, _stream())
-    _lib.check(rc, "mft_conv2d_nhwc(gemm)")
+    _lib.call("mft_conv2d_nhwc", _p(a), lda, _p(w_pk), _p(bias), _p(out), ldo, M, 1, 1, K, N, 1, 1, 1, 0, rows_per_group, wgs, _stream())
     return out
 
 
@@ -360,7 +345,7 @@ def gemm_rk(a, K, w_pk, N, bias=None, out=None, ldo=None):
         out = torch.empty((M, ldo), device=a.device, dtype=torch.float32)
     else:
         ldo = out.shape[1]
-    _lib.check(_lib.lib().mft_gemm_rk(_p(a), lda, _p(w_pk), w_pk.shape[0], K, _p(bias), _p(out), ldo, M, N, _stream()), "mft_gemm_rk")
+    _lib.call("mft_gemm_rk", _p(a), lda, _p(w_pk), w_pk.shape[0], K, _p(bias), _p(out), ldo, M, N, _stream())
     return out
 
 
@@ -377,21 +362,18 @@ def conv2d_dgrad(dy, w_pk, Cin, KH, KW, pad, imgs_per_group=0, out=None, stride=
         nws = _ksplit_ws(n * H * W, Cin, KH * KW * Cout)
         if nws:
             ws = torch.empty((nws,), device=dy.device, dtype=torch.float32)
-            rc = _lib.lib().mft_conv2d_dgrad_nhwc_ksplit(_p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride, pad,
-                                                         _p(ws), _stream())
-            _lib.check(rc, "mft_conv2d_dgrad_nhwc_ksplit")
+            _lib.call("mft_conv2d_dgrad_nhwc_ksplit", _p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride, pad,
+                      _p(ws), _stream())
             return out
     if w_pk.dim() == 3 and 1 < w_pk.shape[0] <= SMALL_GROUPS and Cin % 64 == 0 and stride == 1 and imgs_per_group > 0:
         nws = _ksplit_ws(imgs_per_group * H * W, Cin, KH * KW * Cout, w_pk.shape[0])
         if nws:
             ws = torch.empty((nws,), device=dy.device, dtype=torch.float32)
-            rc = _lib.lib().mft_conv2d_dgrad_nhwc_ksplit_grouped(_p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride,
-                                                                 pad, imgs_per_group, wgs, _p(ws), _stream())
-            _lib.check(rc, "mft_conv2d_dgrad_nhwc_ksplit_grouped")
+            _lib.call("mft_conv2d_dgrad_nhwc_ksplit_grouped", _p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride,
+                      pad, imgs_per_group, wgs, _p(ws), _stream())
             return out
-    rc = _lib.lib().mft_conv2d_dgrad_nhwc(_p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride, pad,
-                                          imgs_per_group, wgs, _stream())
-    _lib.check(rc, "mft_conv2d_dgrad_nhwc")
+    _lib.call("mft_conv2d_dgrad_nhwc", _p(dy), Cout, _p(w_pk), _p(out), Cin, n, H, W, Cin, Cout, KH, KW, stride, pad, imgs_per_group, wgs,
+              _stream())
     return out
 
 
@@ -406,9 +388,8 @@ def conv2d_wgrad(x, dy, Cout, KH, KW, stride, pad, imgs_per_group=0, out=None, l
         out = torch.empty((groups, Cout, K), device=x.device, dtype=torch.float32)
     nws = int(_lib.lib().mft_conv2d_wgrad_ws_floats(n, H, W, Cin, Cout, KH, KW, stride, pad, imgs_per_group))
     ws = torch.empty((nws,), device=x.device, dtype=torch.float32) if nws > 0 else None
-    rc = _lib.lib().mft_conv2d_wgrad_nhwc(_p(x), Cin, _p(dy), dy.shape[-1] if ldy is None else ldy, _p(out), n, H, W,
-                                          Cin, Cout, KH, KW, stride, pad, imgs_per_group, Cout * K, _p(ws), _stream())
-    _lib.check(rc, "mft_conv2d_wgrad_nhwc")
+    _lib.call("mft_conv2d_wgrad_nhwc", _p(x), Cin, _p(dy), dy.shape[-1] if ldy is None else ldy, _p(out), n, H, W, Cin, Cout, KH, KW,
+              stride, pad, imgs_per_group, Cout * K, _p(ws), _stream())
     return out
 
 
@@ -422,17 +403,9 @@ def conv2d_wgrad_oihw(x, dy, Cout, KH, KW, stride, pad, cin_valid=0, cout_valid=
         out = torch.empty((cout_valid or Cout, cin_valid or Cin, KH, KW), device=x.device, dtype=torch.float32)
     ws = torch.empty((int(_lib.lib().mft_conv2d_wgrad_oihw_ws_floats(n, H, W, Cin, Cout, KH, KW, stride, pad)),), device=x.device,
                      dtype=torch.float32)
-    rc = _lib.lib().mft_conv2d_wgrad_oihw(_p(x), Cin, _p(dy), dy.shape[-1], _p(out), n, H, W, Cin, Cout, KH, KW, stride, pad,
-                                          cin_valid, cout_valid, _p(ws), _stream())
-    _lib.check(rc, "mft_conv2d_wgrad_oihw")
+    _lib.call("mft_conv2d_wgrad_oihw", _p(x), Cin, _p(dy), dy.shape[-1], _p(out), n, H, W, Cin, Cout, KH, KW, stride, pad, cin_valid,
+              cout_valid, _p(ws), _stream())
     return out
-
-
-class _WgradJob(ctypes.Structure):
-    """MftWgradJob (include/mft_hip.h)"""
-    _fields_ = [("inp", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("ws", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int) for n in ("ldi", "ldy", "n_img", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad", "cin_valid",
-                                            "cout_valid", "reserved")]
 
 
 class WgradBatch:
@@ -470,9 +443,10 @@ class WgradBatch:
 
     def flush(self):
         if self.jobs:
-            arr = (_WgradJob * len(self.jobs))(*[_WgradJob(*j) for j in self.jobs])
+            job = _lib.struct("MftWgradJob")
+            arr = (job * len(self.jobs))(*[job(*j) for j in self.jobs])
             dev = self.keep[0][0].device
-            _lib.check(_lib.lib().mft_conv2d_wgrad_oihw_multi(arr, len(self.jobs), _stream(dev)), "mft_conv2d_wgrad_oihw_multi")
+            _lib.call("mft_conv2d_wgrad_oihw_multi", arr, len(self.jobs), _stream(dev))
         for fn in self.after:
             fn()
         self.jobs, self.keep, self.after = [], [], []
@@ -487,15 +461,11 @@ def conv2d_wgrad_adam(x, dy, w, m, v, Cout, KH, KW, stride, pad, step, imgs_per_
     n, H, W, Cin = x.shape
     K = KH * KW * Cin
     if hyper is not None:
-        rc = _lib.lib().mft_conv2d_wgrad_adam_nhwc_dev(_p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dw), n, H, W, Cin,
-                                                       Cout, KH, KW, stride, pad, imgs_per_group, Cout * K, _p(hyper), beta1,
-                                                       beta2, eps, _stream())
-        _lib.check(rc, "mft_conv2d_wgrad_adam_nhwc_dev")
+        _lib.call("mft_conv2d_wgrad_adam_nhwc_dev", _p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dw), n, H, W, Cin, Cout, KH, KW,
+                  stride, pad, imgs_per_group, Cout * K, _p(hyper), beta1, beta2, eps, _stream())
         return
-    rc = _lib.lib().mft_conv2d_wgrad_adam_nhwc(_p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dw), n, H, W, Cin,
-                                               Cout, KH, KW, stride, pad, imgs_per_group, Cout * K, step, lr, beta1,
-                                               beta2, eps, _stream())
-    _lib.check(rc, "mft_conv2d_wgrad_adam_nhwc")
+    _lib.call("mft_conv2d_wgrad_adam_nhwc", _p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dw), n, H, W, Cin, Cout, KH, KW, stride, pad,
+              imgs_per_group, Cout * K, step, lr, beta1, beta2, eps, _stream())
 
 
 WF_RAW, WF_ENTRY, WF_EXIT = 0, 1, 2
@@ -510,15 +480,12 @@ def wgrad_adam_next_forward(x, dy, w, m, v, KH, KW, stride, pad, step, imgs_per_
     _f32c(dy)
     n, H, W, Cin = x.shape
     Cout = dy.shape[-1]
-    rc = _lib.lib().mft_wgrad_adam_next_forward(
+    return _lib.try_call(
+        "mft_wgrad_adam_next_forward",
         _p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dw), n, H, W, Cin, Cout, KH, KW, stride, pad, imgs_per_group,
         Cout * KH * KW * Cin, 1 if hyper is not None else step, _p(hyper), lr, beta1, beta2, eps, _p(x_next), mode, _p(raw), _p(act),
         _p(gamma), _p(beta), gbs, _p(mean), _p(rstd), _p(sc_raw), _p(gamma_s), _p(beta_s), _p(mean_s), _p(rstd_s), _p(pooled),
         BN_EPS, _stream())
-    if rc == _lib.MFT_EINVAL:
-        return False
-    _lib.check(rc, "mft_wgrad_adam_next_forward")
-    return True
 
 
 def conv2d_wgrad_adam_dgrad(x, dy, w, m, v, dxp, step, imgs_per_group, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, hyper=None):
@@ -528,15 +495,10 @@ def conv2d_wgrad_adam_dgrad(x, dy, w, m, v, dxp, step, imgs_per_group, lr=0.01, 
     Cout = dy.shape[-1]
     gs = w.shape[1] * w.shape[2]
     if hyper is not None:
-        rc = _lib.lib().mft_conv2d_wgrad_adam_dgrad_nhwc_dev(_p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dxp), n, H, W, Cin,
-                                                             Cout, imgs_per_group, gs, _p(hyper), beta1, beta2, eps, _stream())
-    else:
-        rc = _lib.lib().mft_conv2d_wgrad_adam_dgrad_nhwc(_p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dxp), n, H, W, Cin, Cout,
-                                                         imgs_per_group, gs, step, lr, beta1, beta2, eps, _stream())
-    if rc == _lib.MFT_EINVAL:
-        return False
-    _lib.check(rc, "mft_conv2d_wgrad_adam_dgrad_nhwc")
-    return True
+        return _lib.try_call("mft_conv2d_wgrad_adam_dgrad_nhwc_dev", _p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dxp), n, H, W, Cin,
+                             Cout, imgs_per_group, gs, _p(hyper), beta1, beta2, eps, _stream())
+    return _lib.try_call("mft_conv2d_wgrad_adam_dgrad_nhwc", _p(x), Cin, _p(dy), Cout, _p(w), _p(m), _p(v), _p(dxp), n, H, W, Cin, Cout,
+                         imgs_per_group, gs, step, lr, beta1, beta2, eps, _stream())
 
 
 # ------------------------------------------------------------------------------------ batch norm
@@ -551,9 +513,8 @@ def bn_stats(x2d, C, rows_per_group, n_groups, running_mean=None, running_var=No
     rstd = torch.empty_like(mean)
     nws = _lib.lib().mft_bn_stats_ws_floats(C, rows_per_group, n_groups)
     ws = torch.empty((max(int(nws), 1),), device=x2d.device, dtype=torch.float32)
-    rc = _lib.lib().mft_bn_stats(_p(x2d), ld, C, rows_per_group, n_groups, eps, _p(mean), _p(rstd), _p(ws),
-                                 _p(running_mean), _p(running_var), momentum, _p(num_batches_tracked), _stream())
-    _lib.check(rc, "mft_bn_stats")
+    _lib.call("mft_bn_stats", _p(x2d), ld, C, rows_per_group, n_groups, eps, _p(mean), _p(rstd), _p(ws), _p(running_mean), _p(running_var),
+              momentum, _p(num_batches_tracked), _stream())
     return mean, rstd
 
 
@@ -573,24 +534,16 @@ def bn_apply(x2d, C, rows_per_group, n_groups, mean, rstd, gamma, beta, act=ACT_
     rm = rr = rg = rb = None
     if res_bn is not None:
         rm, rr, rg, rb = res_bn
-    rc = _lib.lib().mft_bn_apply(_p(x2d), x2d.shape[-1], _p(out), out.shape[-1], C, rows_per_group, n_groups,
-                                 _p(mean), _p(rstd), _p(gamma), _p(beta), gb_group_stride,
-                                 _p(res), 0 if res is None else res.shape[-1], _p(rm), _p(rr), _p(rg), _p(rb),
-                                 act, slope, _stream())
-    _lib.check(rc, "mft_bn_apply")
+    _lib.call("mft_bn_apply", _p(x2d), x2d.shape[-1], _p(out), out.shape[-1], C, rows_per_group, n_groups, _p(mean), _p(rstd), _p(gamma),
+              _p(beta), gb_group_stride, _p(res), 0 if res is None else res.shape[-1], _p(rm), _p(rr), _p(rg), _p(rb), act, slope,
+              _stream())
     return out
-
-
-class _BnStatsJob(ctypes.Structure):
-    """MftBnStatsJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "mean", "rstd", "ws", "running_mean", "running_var", "nbt")] + \
-               [(n, ctypes.c_int) for n in ("ldx", "C", "rows_per_group", "n_groups")] + [("eps", ctypes.c_float), ("momentum", ctypes.c_float)]
 
 
 def bn_stats_multi(jobs, momentum=0.1, eps=BN_EPS):
     """``jobs``: list of (x2d, C, rows_per_group, n_groups, running_mean | None, running_var | None, num_batches_tracked | None) --
     bn_stats of each in ONE launch pair (mft_bn_stats_multi, up to 8 jobs); returns [(mean, rstd), ...]."""
-    arr = (_BnStatsJob * len(jobs))()
+    arr = (_lib.struct("MftBnStatsJob") * len(jobs))()
     out, keep = [], []
     for a, (x, C, rpg, ng, rm, rv, nbt) in zip(arr, jobs):
         _f32c(x)
@@ -600,21 +553,12 @@ def bn_stats_multi(jobs, momentum=0.1, eps=BN_EPS):
         a.x, a.mean, a.rstd, a.ws = x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr()
         a.running_mean = None if rm is None else rm.data_ptr()
         a.running_var = None if rv is None else rv.data_ptr()
-        a.nbt = None if nbt is None else nbt.data_ptr()
+        a.num_batches_tracked = None if nbt is None else nbt.data_ptr()
         a.ldx, a.C, a.rows_per_group, a.n_groups, a.eps, a.momentum = x.shape[-1], C, rpg, ng, eps, momentum
         out.append((mean, rstd))
         keep.append(ws)
-    _lib.check(_lib.lib().mft_bn_stats_multi(arr, len(jobs), _stream(jobs[0][0].device)), "mft_bn_stats_multi")
+    _lib.call("mft_bn_stats_multi", arr, len(jobs), _stream(jobs[0][0].device))
     return out
-
-
-class _BnFwdJob(ctypes.Structure):
-    """MftBnFwdJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "y", "gamma", "beta", "mean", "rstd", "running_mean", "running_var", "nbt", "res",
-                                                "res_gamma", "res_beta", "res_mean", "res_rstd", "res_running_mean", "res_running_var",
-                                                "res_nbt")] + \
-               [(n, ctypes.c_int) for n in ("ldx", "ldy", "ldr", "C", "rows_per_group", "n_groups", "act")] + \
-               [(n, ctypes.c_float) for n in ("eps", "momentum", "slope")]
 
 
 def bn_forward_small_ok(C, rows_per_group):
@@ -636,11 +580,11 @@ def bn_forward_small(x2d, C, rows_per_group, n_groups, gamma, beta, act=ACT_NONE
     assert out_col >= 0 and out_col + C <= out.shape[-1]
     mean = torch.empty((n_groups, C), device=dev, dtype=torch.float32)
     rstd = torch.empty_like(mean)
-    j = _BnFwdJob()
+    j = _lib.struct("MftBnFwdJob")()
     j.x, j.y, j.gamma, j.beta, j.mean, j.rstd = (t.data_ptr() for t in (x2d, out, gamma, beta, mean, rstd))
     j.y = out.data_ptr() + 4 * out_col
     rm, rv, nbt = running if running is not None else (None, None, None)
-    j.running_mean, j.running_var, j.nbt = (None if t is None else t.data_ptr() for t in (rm, rv, nbt))
+    j.running_mean, j.running_var, j.num_batches_tracked = (None if t is None else t.data_ptr() for t in (rm, rv, nbt))
     rmean = rrstd = None
     if res is not None:
         _f32c(res)
@@ -651,28 +595,20 @@ def bn_forward_small(x2d, C, rows_per_group, n_groups, gamma, beta, act=ACT_NONE
             rrstd = torch.empty_like(rmean)
             j.res_gamma, j.res_beta, j.res_mean, j.res_rstd = rg.data_ptr(), rb.data_ptr(), rmean.data_ptr(), rrstd.data_ptr()
             rrm, rrv, rnbt = rrun if rrun is not None else (None, None, None)
-            j.res_running_mean, j.res_running_var, j.res_nbt = (None if t is None else t.data_ptr() for t in (rrm, rrv, rnbt))
+            j.res_running_mean, j.res_running_var, j.res_num_batches_tracked = (None if t is None else t.data_ptr() for t in (rrm, rrv, rnbt))
     j.ldx, j.ldy, j.C, j.rows_per_group, j.n_groups, j.act = x2d.shape[-1], out.shape[-1], C, rows_per_group, n_groups, act
     j.eps, j.momentum, j.slope = eps, momentum, slope
-    _lib.check(_lib.lib().mft_bn_forward_small(ctypes.byref(j), _stream(dev)), "mft_bn_forward_small")
+    _lib.call("mft_bn_forward_small", ctypes.byref(j), _stream(dev))
     if rmean is not None:
         return out, mean, rstd, rmean, rrstd
     return out, mean, rstd
-
-
-class _BnBwdJob(ctypes.Structure):
-    """MftBnBwdJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "dy", "y_act", "dx", "mean", "rstd", "gamma", "dgamma", "dbeta", "ws", "dgamma_sum",
-                                                "dbeta_sum", "dbias_zero")] + \
-               [(n, ctypes.c_int) for n in ("ldx", "lddy", "ldya", "lddx", "C", "rows_per_group", "n_groups", "act")] + \
-               [("slope", ctypes.c_float), ("reserved", ctypes.c_int)]
 
 
 def bn_backward_multi(jobs):
     """``jobs``: list of (x2d, dy2d, y_act | None, C, rows, groups, mean, rstd, gamma, act) -- BatchNorm backward (+ activation
     derivative) of each in ONE launch triple (mft_bn_backward_act_multi); returns [(dx, dgamma [C], dbeta [C]), ...] with the
     parameter gradients summed over the groups."""
-    arr = (_BnBwdJob * len(jobs))()
+    arr = (_lib.struct("MftBnBwdJob") * len(jobs))()
     out, keep = [], []
     for a, (x, dy, ya, C, rows, groups, mean, rstd, gamma, act) in zip(arr, jobs):
         _f32c(x)
@@ -692,14 +628,8 @@ def bn_backward_multi(jobs):
         a.C, a.rows_per_group, a.n_groups, a.act, a.slope = C, rpg, groups, act, LRELU_SLOPE
         out.append((dx, dg, db))
         keep.append(ws)
-    _lib.check(_lib.lib().mft_bn_backward_act_multi(arr, len(jobs), _stream(jobs[0][0].device)), "mft_bn_backward_act_multi")
+    _lib.call("mft_bn_backward_act_multi", arr, len(jobs), _stream(jobs[0][0].device))
     return out
-
-
-class _BnApplyJob(ctypes.Structure):
-    """MftBnApplyJob (include/mft_hip.h)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "y", "mean", "rstd", "gamma", "beta")] + \
-               [(n, ctypes.c_int) for n in ("ldx", "ldy", "C", "rows_per_group", "n_groups", "act")] + [("slope", ctypes.c_float), ("reserved", ctypes.c_int)]
 
 
 def bn_apply_multi(jobs):
@@ -707,12 +637,12 @@ def bn_apply_multi(jobs):
     launch per 16 jobs (mft_bn_apply_multi); returns the list of outputs."""
     if not jobs:
         return []
-    arr = (_BnApplyJob * len(jobs))()
+    arr = (_lib.struct("MftBnApplyJob") * len(jobs))()
     for a, (x, C, rpg, ng, mean, rstd, gamma, beta, act, out) in zip(arr, jobs):
         _f32c(x)
         a.x, a.y, a.mean, a.rstd, a.gamma, a.beta = (t.data_ptr() for t in (x, out, mean, rstd, gamma, beta))
         a.ldx, a.ldy, a.C, a.rows_per_group, a.n_groups, a.act, a.slope = x.shape[-1], out.shape[-1], C, rpg, ng, act, LRELU_SLOPE
-    _lib.check(_lib.lib().mft_bn_apply_multi(arr, len(jobs), _stream(jobs[0][0].device)), "mft_bn_apply_multi")
+    _lib.call("mft_bn_apply_multi", arr, len(jobs), _stream(jobs[0][0].device))
     return [j[-1] for j in jobs]
 
 
@@ -721,9 +651,7 @@ def bn_relu_maxpool(x, mean, rstd, gamma, beta, imgs_per_group=0):
     n, H, W, C = x.shape
     OH, OW = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = torch.empty((n, OH, OW, C), device=x.device, dtype=torch.float32)
-    rc = _lib.lib().mft_bn_relu_maxpool(_p(x), _p(y), n, H, W, C, imgs_per_group, _p(mean), _p(rstd), _p(gamma),
-                                        _p(beta), _stream())
-    _lib.check(rc, "mft_bn_relu_maxpool")
+    _lib.call("mft_bn_relu_maxpool", _p(x), _p(y), n, H, W, C, imgs_per_group, _p(mean), _p(rstd), _p(gamma), _p(beta), _stream())
     return y
 
 
@@ -734,9 +662,8 @@ def bn_relu_maxpool_gather(cache, src_idx, n_img, mean, rstd, gamma, beta, imgs_
     OH, OW = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     if out is None:
         out = torch.empty((n_img, OH, OW, C), device=cache.device, dtype=torch.float32)
-    rc = _lib.lib().mft_bn_relu_maxpool_gather(_p(cache), _p(src_idx), _p(out), n_img, H, W, C, imgs_per_group, _p(mean),
-                                               _p(rstd), _p(gamma), _p(beta), _stream())
-    _lib.check(rc, "mft_bn_relu_maxpool_gather")
+    _lib.call("mft_bn_relu_maxpool_gather", _p(cache), _p(src_idx), _p(out), n_img, H, W, C, imgs_per_group, _p(mean), _p(rstd), _p(gamma),
+              _p(beta), _stream())
     return out
 
 
@@ -746,7 +673,7 @@ def bn_image_moments(x):
     n, H, W, C = x.shape
     mean = torch.empty((n, C), device=x.device, dtype=torch.float32)
     m2 = torch.empty_like(mean)
-    _lib.check(_lib.lib().mft_bn_image_moments(_p(x), C, C, H * W, n, _p(mean), _p(m2), _stream()), "mft_bn_image_moments")
+    _lib.call("mft_bn_image_moments", _p(x), C, C, H * W, n, _p(mean), _p(m2), _stream())
     return mean, m2
 
 
@@ -756,9 +683,8 @@ def bn_combine_moments(mean_img, m2_img, idx_i32, rows_per_img, imgs_per_group, 
     if mean is None:
         mean = torch.empty((n_groups, C), device=mean_img.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-    rc = _lib.lib().mft_bn_combine_moments(_p(mean_img), _p(m2_img), _p(idx_i32), C, rows_per_img, imgs_per_group,
-                                           n_groups, eps, _p(mean), _p(rstd), _stream())
-    _lib.check(rc, "mft_bn_combine_moments")
+    _lib.call("mft_bn_combine_moments", _p(mean_img), _p(m2_img), _p(idx_i32), C, rows_per_img, imgs_per_group, n_groups, eps, _p(mean),
+              _p(rstd), _stream())
     return mean, rstd
 
 
@@ -766,7 +692,7 @@ def global_avgpool(x):
     _f32c(x)
     n, H, W, C = x.shape
     y = torch.empty((n, C), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_global_avgpool(_p(x), _p(y), n, H * W, C, _stream()), "mft_global_avgpool")
+    _lib.call("mft_global_avgpool", _p(x), _p(y), n, H * W, C, _stream())
     return y
 
 
@@ -775,8 +701,7 @@ def avgpool_relu_backward(dfeat, out):
     _f32c(out)
     n, H, W, C = out.shape
     d = torch.empty_like(out)
-    _lib.check(_lib.lib().mft_avgpool_relu_backward(_p(dfeat), _p(out), _p(d), n, H * W, C, _stream()),
-               "mft_avgpool_relu_backward")
+    _lib.call("mft_avgpool_relu_backward", _p(dfeat), _p(out), _p(d), n, H * W, C, _stream())
     return d
 
 
@@ -788,11 +713,9 @@ def bn_backward(x2d, dy2d, C, rows_per_group, n_groups, mean, rstd, gamma, relu_
     dx = torch.empty_like(x2d) if need_dx else None
     dg = torch.empty((n_groups, C), device=x2d.device, dtype=torch.float32)
     db = torch.empty_like(dg)
-    rc = _lib.lib().mft_bn_backward(_p(x2d), x2d.shape[-1], _p(dy2d), dy2d.shape[-1], _p(relu_out),
-                                    0 if relu_out is None else relu_out.shape[-1], _p(dx),
-                                    0 if dx is None else dx.shape[-1], C, rows_per_group, n_groups, _p(mean), _p(rstd),
-                                    _p(gamma), gb_group_stride, _p(dg), _p(db), _stream())
-    _lib.check(rc, "mft_bn_backward")
+    _lib.call("mft_bn_backward", _p(x2d), x2d.shape[-1], _p(dy2d), dy2d.shape[-1], _p(relu_out),
+              0 if relu_out is None else relu_out.shape[-1], _p(dx), 0 if dx is None else dx.shape[-1], C, rows_per_group, n_groups,
+              _p(mean), _p(rstd), _p(gamma), gb_group_stride, _p(dg), _p(db), _stream())
     return dx, dg, db
 
 
@@ -804,9 +727,7 @@ def cross_entropy(logits, labels_i32, rows_per_group, n_groups, need_grad=True):
     rows, C = logits.shape
     buf = torch.empty((n_groups + rows,), device=logits.device, dtype=torch.float32)
     d = torch.empty_like(logits) if need_grad else None
-    rc = _lib.lib().mft_cross_entropy(_p(logits), C, _p(labels_i32), C, rows_per_group, n_groups, _p(buf), _p(d),
-                                      _stream())
-    _lib.check(rc, "mft_cross_entropy")
+    _lib.call("mft_cross_entropy", _p(logits), C, _p(labels_i32), C, rows_per_group, n_groups, _p(buf), _p(d), _stream())
     return buf[:n_groups], d
 
 
@@ -814,7 +735,7 @@ def softmax_rows(x):
     _f32c(x)
     rows, C = x.shape
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().mft_softmax_rows(_p(x), C, _p(y), C, C, rows, _stream()), "mft_softmax_rows")
+    _lib.call("mft_softmax_rows", _p(x), C, _p(y), C, C, rows, _stream())
     return y
 
 
@@ -834,8 +755,8 @@ def proto_scores(feats, episodes, n_way, n_support, n_query, softmax=False, out=
     if out is not None and (tuple(out.shape) != (rows, n_way) or not out.is_contiguous()):
         raise ValueError("proto_scores: out must be a contiguous [%d, %d] tensor" % (rows, n_way))
     y = out if out is not None else torch.empty((rows, n_way), device=feats.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_proto_scores(_p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(y),
-                                           1 if softmax else 0, _stream()), "mft_proto_scores")
+    _lib.call("mft_proto_scores", _p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(y), 1 if softmax else 0,
+              _stream())
     return y
 
 
@@ -849,8 +770,8 @@ def proto_backward(feats, dscores, episodes, n_way, n_support, n_query, out=None
         raise ValueError("proto_backward: out must be a contiguous tensor shaped like feats")
     D = feats.shape[1]
     dx = out if out is not None else torch.empty((feats.shape[0], D), device=feats.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_proto_backward(_p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(dscores),
-                                             dscores.stride(0), _p(dx), dx.stride(0), _stream()), "mft_proto_backward")
+    _lib.call("mft_proto_backward", _p(feats), feats.stride(0), episodes, n_way, n_support, n_query, D, _p(dscores), dscores.stride(0),
+              _p(dx), dx.stride(0), _stream())
     return dx
 
 
@@ -877,8 +798,8 @@ def dist_linear_forward(x, g, v, scale, softmax=False):
     if n_groups < 1 or g.numel() != n_groups * C or x.shape[1] != D or x.shape[0] % n_groups:
         raise ValueError("dist_linear_forward: x %s, g %s, v %s do not fit" % (tuple(x.shape), tuple(g.shape), tuple(v.shape)))
     y = torch.empty((x.shape[0], C), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_dist_linear_forward(_p(x), x.stride(0), n_groups, x.shape[0] // n_groups, _p(v), _p(g), C, D,
-                                                  float(scale), _p(y), 1 if softmax else 0, _stream()), "mft_dist_linear_forward")
+    _lib.call("mft_dist_linear_forward", _p(x), x.stride(0), n_groups, x.shape[0] // n_groups, _p(v), _p(g), C, D, float(scale), _p(y),
+              1 if softmax else 0, _stream())
     return y
 
 
@@ -896,9 +817,8 @@ def dist_linear_backward(x, g, v, scale, dscores, need_dx=True):
     dx = torch.empty((x.shape[0], D), device=x.device, dtype=torch.float32) if need_dx else None
     dv = torch.empty_like(v)
     dg = torch.empty_like(g)
-    _lib.check(_lib.lib().mft_dist_linear_backward(_p(x), x.stride(0), x.shape[0], _p(v), _p(g), C, D, float(scale), _p(dscores),
-                                                   dscores.stride(0), _p(dx), D, _p(dv), _p(dg), _stream()),
-               "mft_dist_linear_backward")
+    _lib.call("mft_dist_linear_backward", _p(x), x.stride(0), x.shape[0], _p(v), _p(g), C, D, float(scale), _p(dscores), dscores.stride(0),
+              _p(dx), D, _p(dv), _p(dg), _stream())
     return dx, dv, dg
 
 
@@ -917,9 +837,8 @@ def dist_head_sgd_run(z_support, y_support, table, v, g, scale, lr=0.01, momentu
             or table.shape[0] != G:
         raise ValueError("dist_head_sgd_run: z %s, y %s, table %s, v %s, g %s do not fit"
                          % (tuple(z_support.shape), tuple(y_support.shape), tuple(table.shape), tuple(v.shape), tuple(g.shape)))
-    _lib.check(_lib.lib().mft_dist_head_sgd_run(_p(z_support), _p(y_support), _p(table), G, S, D, n_way, table.shape[1],
-                                                table.shape[2], _p(v), _p(g), float(scale), lr, momentum, dampening, weight_decay,
-                                                _stream()), "mft_dist_head_sgd_run")
+    _lib.call("mft_dist_head_sgd_run", _p(z_support), _p(y_support), _p(table), G, S, D, n_way, table.shape[1], table.shape[2], _p(v),
+              _p(g), float(scale), lr, momentum, dampening, weight_decay, _stream())
 
 
 def dist_head_step(feat, labels, v, g, mv, vv, mg, vg, scale, step, dfeat=None, loss=None, lr=0.01, beta1=0.9, beta2=0.999,
@@ -946,15 +865,80 @@ def dist_head_step(feat, labels, v, g, mv, vv, mg, vg, scale, step, dfeat=None, 
     if loss is None:
         loss = torch.empty((G,), device=feat.device, dtype=torch.float32)
     _dist_rows(dfeat, "dist_head_step")
-    _lib.check(_lib.lib().mft_dist_head_step(_p(feat), feat.stride(0), _p(labels), k, G, n_way, D, float(scale), _p(v), _p(g),
-                                             _p(mv), _p(vv), _p(mg), _p(vg), _p(dfeat), dfeat.stride(0), _p(loss), int(step), lr,
-                                             beta1, beta2, eps, weight_decay, _stream()), "mft_dist_head_step")
+    _lib.call("mft_dist_head_step", _p(feat), feat.stride(0), _p(labels), k, G, n_way, D, float(scale), _p(v), _p(g), _p(mv), _p(vv),
+              _p(mg), _p(vg), _p(dfeat), dfeat.stride(0), _p(loss), int(step), lr, beta1, beta2, eps, weight_decay, _stream())
     return dfeat, loss
+
+
+def _linear_head(W, b, what):
+    _f32c(W)
+    _f32c(b)
+    if W.dim() != 3 or tuple(b.shape) != tuple(W.shape[:2]):
+        raise ValueError("%s: W must be [groups, n_way, D] and b [groups, n_way], got %s, %s" % (what, tuple(W.shape), tuple(b.shape)))
+    return W.shape
+
+
+def linear_head_step(feat, labels, W, b, mW, vW, mb, vb, step, dfeat=None, loss=None, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8,
+                     weight_decay=0.001):
+    """dist_head_step with finetune_linear's Linear(D, n_way) head: feat [G * k, D] (row stride free), labels [G * k] int32,
+    W [G, n_way, D] and b [G, n_way] with their Adam moments, all six updated IN PLACE; ``step`` = the 1-based Adam step.
+    -> (dfeat [G * k, D] computed with the pre-update head, loss [G]), both written whole."""
+    _dist_rows(feat, "linear_head_step")
+    G, n_way, D = _linear_head(W, b, "linear_head_step")
+    for t in (mW, vW, mb, vb):
+        _f32c(t)
+    if labels.dtype != torch.int32 or not labels.is_contiguous():
+        raise RuntimeError("linear_head_step: labels must be a contiguous int32 tensor")
+    k = feat.shape[0] // G
+    if feat.shape[0] != G * k or feat.shape[1] != D or labels.numel() != G * k or any(t.shape != W.shape for t in (mW, vW)) \
+            or any(t.shape != b.shape for t in (mb, vb)):
+        raise ValueError("linear_head_step: feat %s, labels %s, W %s, b %s and their moments do not fit"
+                         % (tuple(feat.shape), tuple(labels.shape), tuple(W.shape), tuple(b.shape)))
+    if dfeat is None:
+        dfeat = torch.empty((G * k, D), device=feat.device, dtype=torch.float32)
+    if loss is None:
+        loss = torch.empty((G,), device=feat.device, dtype=torch.float32)
+    _dist_rows(dfeat, "linear_head_step")
+    _lib.call("mft_linear_head_step", _p(feat), feat.stride(0), _p(labels), k, G, n_way, D, _p(W), _p(b), _p(mW), _p(vW), _p(mb), _p(vb),
+              _p(dfeat), dfeat.stride(0), _p(loss), int(step), lr, beta1, beta2, eps, weight_decay, _stream())
+    return dfeat, loss
+
+
+def linear_head_scores(x, W, b, out=None):
+    """softmax(x @ W[g]^T + b[g]) of every group's rows, one launch: x [G * rows, D] (row stride free), W [G, n_way, D],
+    b [G, n_way] -> [G * rows, n_way] (``out``: caller's contiguous buffer)."""
+    _dist_rows(x, "linear_head_scores")
+    G, n_way, D = _linear_head(W, b, "linear_head_scores")
+    if x.shape[1] != D or x.shape[0] % G:
+        raise ValueError("linear_head_scores: x %s, W %s do not fit" % (tuple(x.shape), tuple(W.shape)))
+    if out is None:
+        out = torch.empty((x.shape[0], n_way), device=x.device, dtype=torch.float32)
+    elif tuple(_f32c(out).shape) != (x.shape[0], n_way):
+        raise ValueError("linear_head_scores: out must be %s, got %s" % ((x.shape[0], n_way), tuple(out.shape)))
+    _lib.call("mft_linear_head_scores", _p(x), x.stride(0), x.shape[0] // G, G, n_way, D, _p(W), _p(b), _p(out), _stream())
+    return out
+
+
+def linear_head_adam_run(z_support, y_support, table, W, b, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.001):
+    """dist_head_sgd_run's twin for finetune_linear(freeze_backbone=True): z_support [G, S, D], y_support [G, S] int32,
+    table [G, T, batch] int32 (support row per mini-batch slot, -1 = empty), W [G, n_way, D] and b [G, n_way] updated IN PLACE with
+    torch.optim.Adam semantics (L2 weight decay), every step of every group in one launch."""
+    _f32c(z_support)
+    G, n_way, D = _linear_head(W, b, "linear_head_adam_run")
+    for t in (y_support, table):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError("linear_head_adam_run: labels and index table must be contiguous int32 tensors")
+    S = z_support.shape[1] if z_support.dim() == 3 else -1
+    if tuple(z_support.shape) != (G, S, D) or tuple(y_support.shape) != (G, S) or table.dim() != 3 or table.shape[0] != G:
+        raise ValueError("linear_head_adam_run: z %s, y %s, table %s, W %s do not fit"
+                         % (tuple(z_support.shape), tuple(y_support.shape), tuple(table.shape), tuple(W.shape)))
+    _lib.call("mft_linear_head_adam_run", _p(z_support), _p(y_support), _p(table), G, S, D, n_way, table.shape[1], table.shape[2], _p(W),
+              _p(b), lr, beta1, beta2, eps, weight_decay, _stream())
 
 
 def adam_hyper_advance(step_i32, hyper, lr=0.01, beta1=0.9, beta2=0.999):
     """Device-side t = ++step; hyper = {lr/(1-beta1^t), 1/sqrt(1-beta2^t)} (one tiny launch; graph-capturable)."""
-    _lib.check(_lib.lib().mft_adam_hyper_advance(_p(step_i32), _p(hyper), lr, beta1, beta2, _stream()), "mft_adam_hyper_advance")
+    _lib.call("mft_adam_hyper_advance", _p(step_i32), _p(hyper), lr, beta1, beta2, _stream())
 
 
 def adam_step(p, g, m, v, step, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, hyper=None):
@@ -962,23 +946,17 @@ def adam_step(p, g, m, v, step, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, weigh
     for t in (p, g, m, v):
         _f32c(t)
     if hyper is not None:
-        rc = _lib.lib().mft_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), beta1, beta2, eps, weight_decay,
-                                          _stream())
-        _lib.check(rc, "mft_adam_step_dev")
+        _lib.call("mft_adam_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), beta1, beta2, eps, weight_decay, _stream())
         return
-    rc = _lib.lib().mft_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay,
-                                  _stream())
-    _lib.check(rc, "mft_adam_step")
+    _lib.call("mft_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, beta1, beta2, eps, weight_decay, _stream())
 
 
 def sgd_step(p, g, buf, first_step, lr=0.01, momentum=0.9, dampening=0.9, weight_decay=0.001):
-    rc = _lib.lib().mft_sgd_step(_p(p), _p(g), _p(buf), p.numel(), 1 if first_step else 0, lr, momentum, dampening,
-                                 weight_decay, _stream())
-    _lib.check(rc, "mft_sgd_step")
+    _lib.call("mft_sgd_step", _p(p), _p(g), _p(buf), p.numel(), 1 if first_step else 0, lr, momentum, dampening, weight_decay, _stream())
 
 
 def maml_delta(p, p2, p3):
-    _lib.check(_lib.lib().mft_maml_delta(_p(p), _p(p2), _p(p3), p.numel(), _stream()), "mft_maml_delta")
+    _lib.call("mft_maml_delta", _p(p), _p(p2), _p(p3), p.numel(), _stream())
 
 
 # ------------------------------------------------------------------------------------ gnn glue
@@ -988,8 +966,7 @@ def pair_absdiff(x, N, F, ldd):
     _f32c(x)
     n_graphs = x.shape[0] // N
     d = torch.empty((n_graphs * N * N, ldd), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_pair_absdiff(_p(x), x.shape[1], _p(d), ldd, n_graphs, N, F, _stream()),
-               "mft_pair_absdiff")
+    _lib.call("mft_pair_absdiff", _p(x), x.shape[1], _p(d), ldd, n_graphs, N, F, _stream())
     return d
 
 
@@ -998,7 +975,7 @@ def masked_softmax(s, N):
     _f32c(s)
     n_graphs = s.shape[0] // (N * N)
     A = torch.empty((n_graphs, N, N), device=s.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_masked_softmax(_p(s), s.shape[1], _p(A), n_graphs, N, _stream()), "mft_masked_softmax")
+    _lib.call("mft_masked_softmax", _p(s), s.shape[1], _p(A), n_graphs, N, _stream())
     return A
 
 
@@ -1008,14 +985,12 @@ def graph_aggregate(A, x, F, ldy):
     _f32c(x)
     n_graphs, N, _ = A.shape
     y = torch.empty((n_graphs * N, ldy), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_graph_aggregate(_p(A), _p(x), x.shape[1], _p(y), ldy, n_graphs, N, F, _stream()),
-               "mft_graph_aggregate")
+    _lib.call("mft_graph_aggregate", _p(A), _p(x), x.shape[1], _p(y), ldy, n_graphs, N, F, _stream())
     return y
 
 
 def copy_cols(x, y, col_off, C, act=ACT_NONE, slope=LRELU_SLOPE):
-    _lib.check(_lib.lib().mft_copy_cols(_p(x), x.shape[1], _p(y), y.shape[1], col_off, C, x.shape[0], act, slope,
-                                        _stream()), "mft_copy_cols")
+    _lib.call("mft_copy_cols", _p(x), x.shape[1], _p(y), y.shape[1], col_off, C, x.shape[0], act, slope, _stream())
     return y
 
 
@@ -1024,16 +999,15 @@ def build_graph_nodes(z, n_episodes, n_way, n_support, n_query, ld=256, fold=Fal
     _f32c(z)
     rows = n_episodes * n_query * n_way * (n_support + 1)
     nodes = torch.empty((rows, ld), device=z.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_build_graph_nodes(_p(z), z.shape[1], _p(nodes), ld, n_episodes, n_way, n_support,
-                                                n_query, 1 if fold else 0, _stream()), "mft_build_graph_nodes")
+    _lib.call("mft_build_graph_nodes", _p(z), z.shape[1], _p(nodes), ld, n_episodes, n_way, n_support, n_query, 1 if fold else 0,
+              _stream())
     return nodes
 
 
 def gather_query_scores(out, n_episodes, n_way, n_support, n_query):
     _f32c(out)
     scores = torch.empty((n_episodes * n_way * n_query, n_way), device=out.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_gather_query_scores(_p(out), out.shape[1], _p(scores), n_episodes, n_way, n_support,
-                                                  n_query, _stream()), "mft_gather_query_scores")
+    _lib.call("mft_gather_query_scores", _p(out), out.shape[1], _p(scores), n_episodes, n_way, n_support, n_query, _stream())
     return scores
 
 
@@ -1043,8 +1017,7 @@ def gather_rows(src2d, idx_i32, out=None):
     n = idx_i32.numel()
     if out is None:
         out = torch.empty((n, src2d.shape[1]), device=src2d.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_gather_rows(_p(src2d), _p(idx_i32), _p(out), n, src2d.shape[1], _stream()),
-               "mft_gather_rows")
+    _lib.call("mft_gather_rows", _p(src2d), _p(idx_i32), _p(out), n, src2d.shape[1], _stream())
     return out
 
 
@@ -1063,8 +1036,7 @@ def episode_top1(scores, n_episodes, n_way, n_query, need_pred=False):
                          "1 <= n_way <= %d" % (tuple(scores.shape), scores.stride(0), n_episodes, n_way, n_query, TOP1_MAX_WAY))
     correct = torch.empty((n_episodes,), device=scores.device, dtype=torch.int32)
     pred = torch.empty((rows,), device=scores.device, dtype=torch.int32) if need_pred else None
-    _lib.check(_lib.lib().mft_episode_top1(_p(scores), scores.stride(0), n_episodes, n_way, n_query, _p(correct), _p(pred),
-                                           _stream()), "mft_episode_top1")
+    _lib.call("mft_episode_top1", _p(scores), scores.stride(0), n_episodes, n_way, n_query, _p(correct), _p(pred), _stream())
     return (correct, pred) if need_pred else correct
 
 
@@ -1093,35 +1065,29 @@ def mn_gemm(M, N, a1, lda1, b1, ldb1, K1, c, ldc, ta=False, tb=True, batch=1, a1
             a2_bs=0, b2=None, ldb2=0, b2_bs=0, K2=0, c_in=None, ldci=0, ci_bs=0, bias1=None, bias2=None, c_bs=0):
     """mft_mn_gemm: c[z] = c_in[z] + bias1 + bias2 + op(a1[z]) op(b1[z]) + op(a2[z]) op(b2[z]); tensors are passed for their
     addresses only (views carry the offsets), shapes and strides are the integer arguments."""
-    rc = _lib.lib().mft_mn_gemm(1 if ta else 0, 1 if tb else 0, M, N, batch, _p(a1), lda1, a1_bs, _p(b1), _p(b1_alt), ldb1, b1_bs, K1,
-                                _p(a2), lda2, a2_bs, _p(b2), ldb2, b2_bs, K2, _p(c_in), ldci, ci_bs, _p(bias1), _p(bias2), _p(c),
-                                ldc, c_bs, _stream())
-    _lib.check(rc, "mft_mn_gemm")
+    _lib.call("mft_mn_gemm", 1 if ta else 0, 1 if tb else 0, M, N, batch, _p(a1), lda1, a1_bs, _p(b1), _p(b1_alt), ldb1, b1_bs, K1, _p(a2),
+              lda2, a2_bs, _p(b2), ldb2, b2_bs, K2, _p(c_in), ldci, ci_bs, _p(bias1), _p(bias2), _p(c), ldc, c_bs, _stream())
     return c
 
 
 def lstm_step_forward(gates, ld_g, c_prev, ld_cp, f_add, c_out, h_out, ld_o, rows, batch=1, bs_g=0, bs_cp=0, bs_o=0):
-    rc = _lib.lib().mft_lstm_step_forward(_p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(f_add), MN_D, _p(c_out), _p(h_out), ld_o,
-                                          bs_o, rows, MN_D, batch, _stream())
-    _lib.check(rc, "mft_lstm_step_forward")
+    _lib.call("mft_lstm_step_forward", _p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(f_add), MN_D, _p(c_out), _p(h_out), ld_o, bs_o,
+              rows, MN_D, batch, _stream())
 
 
 def lstm_step_backward(gates, ld_g, c_prev, ld_cp, c_new, ld_cn, dh1, ld_d1, dh2, ld_d2, dc_in, dc_out, ld_dc, rows, batch=1,
                        bs_g=0, bs_cp=0, bs_cn=0, bs_d1=0, bs_d2=0, bs_dc=0, dh_sum=None, dgate_sum=None, accumulate=False):
-    rc = _lib.lib().mft_lstm_step_backward(_p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(c_new), ld_cn, bs_cn, _p(dh1), ld_d1,
-                                           bs_d1, _p(dh2), ld_d2, bs_d2, _p(dc_in), _p(dc_out), ld_dc, bs_dc, _p(dh_sum),
-                                           _p(dgate_sum), 1 if accumulate else 0, rows, MN_D, batch, _stream())
-    _lib.check(rc, "mft_lstm_step_backward")
+    _lib.call("mft_lstm_step_backward", _p(gates), ld_g, bs_g, _p(c_prev), ld_cp, bs_cp, _p(c_new), ld_cn, bs_cn, _p(dh1), ld_d1, bs_d1,
+              _p(dh2), ld_d2, bs_d2, _p(dc_in), _p(dc_out), ld_dc, bs_dc, _p(dh_sum), _p(dgate_sum), 1 if accumulate else 0, rows, MN_D,
+              batch, _stream())
 
 
 def mn_attention_forward(h, G, episodes, Q, S, a, r):
-    _lib.check(_lib.lib().mft_mn_attention_forward(_p(h), _p(G), episodes, Q, S, MN_D, _p(a), _p(r), _stream()),
-               "mft_mn_attention_forward")
+    _lib.call("mft_mn_attention_forward", _p(h), _p(G), episodes, Q, S, MN_D, _p(a), _p(r), _stream())
 
 
 def mn_attention_backward(dr, a, G, dh_in, episodes, Q, S, dlogit, dh_out):
-    _lib.check(_lib.lib().mft_mn_attention_backward(_p(dr), _p(a), _p(G), _p(dh_in), episodes, Q, S, MN_D, _p(dlogit), _p(dh_out),
-                                                    _stream()), "mft_mn_attention_backward")
+    _lib.call("mft_mn_attention_backward", _p(dr), _p(a), _p(G), _p(dh_in), episodes, Q, S, MN_D, _p(dlogit), _p(dh_out), _stream())
 
 
 def mn_readout_forward(h, G, gnorm, episodes, n_way, n_support, n_query):
@@ -1130,9 +1096,8 @@ def mn_readout_forward(h, G, gnorm, episodes, n_way, n_support, n_query):
     M, S = episodes * n_way * n_query, n_way * n_support
     new = lambda *s: torch.empty(s, device=h.device, dtype=torch.float32)  # noqa: E731
     o = {"cos": new(M, S), "p": new(M, S), "hnorm": new(M), "pc": new(M, n_way), "logp": new(M, n_way)}
-    rc = _lib.lib().mft_mn_readout_forward(_p(h), _p(G), _p(gnorm), episodes, n_way, n_support, n_query, MN_D, _p(o["cos"]), _p(o["p"]),
-                                           _p(o["hnorm"]), _p(o["pc"]), _p(o["logp"]), _stream())
-    _lib.check(rc, "mft_mn_readout_forward")
+    _lib.call("mft_mn_readout_forward", _p(h), _p(G), _p(gnorm), episodes, n_way, n_support, n_query, MN_D, _p(o["cos"]), _p(o["p"]),
+              _p(o["hnorm"]), _p(o["pc"]), _p(o["logp"]), _stream())
     return o
 
 
@@ -1141,31 +1106,28 @@ def mn_readout_backward(dlogp, h, G, gnorm, ro, episodes, n_way, n_support, n_qu
     M, S = episodes * n_way * n_query, n_way * n_support
     new = lambda *s: torch.empty(s, device=h.device, dtype=torch.float32)  # noqa: E731
     dcos, dh, dG = new(M, S), new(M, MN_D), new(episodes, S, MN_D)
-    rc = _lib.lib().mft_mn_readout_backward(_p(dlogp), dlogp.stride(0), _p(h), _p(G), _p(gnorm), _p(ro["cos"]), _p(ro["p"]),
-                                            _p(ro["hnorm"]), _p(ro["pc"]), episodes, n_way, n_support, n_query, MN_D, _p(dcos), _p(dh),
-                                            _p(dG), _stream())
-    _lib.check(rc, "mft_mn_readout_backward")
+    _lib.call("mft_mn_readout_backward", _p(dlogp), dlogp.stride(0), _p(h), _p(G), _p(gnorm), _p(ro["cos"]), _p(ro["p"]), _p(ro["hnorm"]),
+              _p(ro["pc"]), episodes, n_way, n_support, n_query, MN_D, _p(dcos), _p(dh), _p(dG), _stream())
     return dh, dG
 
 
 def mn_colsum(x, rows, C, out=None):
     out = torch.empty(C, device=x.device, dtype=torch.float32) if out is None else out
-    _lib.check(_lib.lib().mft_mn_colsum(_p(x), C, C, rows, _p(out), _stream()), "mft_mn_colsum")
+    _lib.call("mft_mn_colsum", _p(x), C, C, rows, _p(out), _stream())
     return out
 
 
 def nll_mean(logp, target, loss_sum=None):
     rows, C = logp.shape
     loss = torch.empty((), device=logp.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_nll_mean(_p(logp), logp.stride(0), _p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(loss),
-                                       _p(loss_sum), _stream()), "mft_nll_mean")
+    _lib.call("mft_nll_mean", _p(logp), logp.stride(0), _p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(loss),
+              _p(loss_sum), _stream())
     return loss
 
 
 def nll_mean_backward(target, rows, C, g):
     d = torch.empty((rows, C), device=target.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mft_nll_mean_backward(_p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(g), _p(d), C,
-                                                _stream()), "mft_nll_mean_backward")
+    _lib.call("mft_nll_mean_backward", _p(target), 1 if target.dtype == torch.int64 else 0, C, rows, _p(g), _p(d), C, _stream())
     return d
 
 
@@ -1207,11 +1169,10 @@ def matching_forward(W, feats, episodes, n_way, n_support, n_query, save=False):
     T = S + 1 if save else 2
     Tg = S if save else 1
     zS, f, fh, fc = new(E, S, D), new(M, D), new(T, M, D), new(T, M, D)
-    _lib.check(_lib.lib().mft_mn_gather(_p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(zS), _p(f), _p(fh[0]), _stream()),
-               "mft_mn_gather")
+    _lib.call("mft_mn_gather", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(zS), _p(f), _p(fh[0]), _stream())
     eg, eh, ec = mn_encoder_forward(W, zS, E, S)
     G, gnorm = new(E, S, D), new(E, S)
-    _lib.check(_lib.lib().mft_mn_encode_combine(_p(zS), _p(eh[0]), _p(eh[1]), E, S, D, _p(G), _p(gnorm), _stream()), "mft_mn_encode_combine")
+    _lib.call("mft_mn_encode_combine", _p(zS), _p(eh[0]), _p(eh[1]), E, S, D, _p(G), _p(gnorm), _stream())
     # FCE: the f half of the cell's input part does not change over the S steps
     wih, whh = W["FCE.lstmcell.weight_ih"], W["FCE.lstmcell.weight_hh"]
     Pf = mn_gemm(M, 4 * D, f, D, wih, 2 * D, D, new(M, 4 * D), 4 * D, bias1=W["FCE.lstmcell.bias_ih"], bias2=W["FCE.lstmcell.bias_hh"])
@@ -1289,8 +1250,7 @@ def matching_backward(W, tape, dlogp):
         g["G_encoder.bias_hh_l0" + sfx] = mn_colsum(eg[d], E * S, 4 * D)
     per = n_way * (n_support + n_query)
     dfeats = new(E * per, D)
-    _lib.check(_lib.lib().mft_mn_scatter_backward(_p(dzS), _p(df), _p(dh), E, n_way, n_support, n_query, D, _p(dfeats), D, _stream()),
-               "mft_mn_scatter_backward")
+    _lib.call("mft_mn_scatter_backward", _p(dzS), _p(df), _p(dh), E, n_way, n_support, n_query, D, _p(dfeats), D, _stream())
     return dfeats, g
 
 
@@ -1341,12 +1301,11 @@ def ridge_forward(feats, scale, episodes, n_way, n_support, n_query, softmax=Fal
     E, D, S, Q = episodes, RIDGE_D, n_way * n_support, n_way * n_query
     new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
     A, alpha, W, scores = new(E, S, S), new(E, S, n_way), new(E, n_way, D), new(E * Q, n_way)
-    h, ld = _lib.lib(), feats.stride(0)
-    _lib.check(h.mft_ridge_gram(_p(feats), ld, E, n_way, n_support, n_query, D, float(lambda_reg), _p(A), _stream()), "mft_ridge_gram")
-    _lib.check(h.mft_ridge_factor_solve(_p(feats), ld, E, n_way, n_support, n_query, D, _p(A), _p(alpha), _p(W), _stream()),
-               "mft_ridge_factor_solve")
-    _lib.check(h.mft_ridge_scores(_p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
-                                  _stream()), "mft_ridge_scores")
+    ld = feats.stride(0)
+    _lib.call("mft_ridge_gram", _p(feats), ld, E, n_way, n_support, n_query, D, float(lambda_reg), _p(A), _stream())
+    _lib.call("mft_ridge_factor_solve", _p(feats), ld, E, n_way, n_support, n_query, D, _p(A), _p(alpha), _p(W), _stream())
+    _lib.call("mft_ridge_scores", _p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
+              _stream())
     if not save:
         return scores, None
     return scores, dict(feats=feats, scale=scale, L=A, alpha=alpha, W=W, shape=(E, n_way, n_support, n_query))
@@ -1367,12 +1326,11 @@ def ridge_backward(tape, dscores):
     new = lambda *s: torch.empty(s, device=feats.device, dtype=torch.float32)  # noqa: E731
     dfeats, dW, dscale = new(feats.shape[0], D), new(E, n_way, D), new(1)
     part = torch.empty(E * 8, device=feats.device, dtype=torch.float64)
-    h, ld = _lib.lib(), feats.stride(0)
-    _lib.check(h.mft_ridge_backward_query(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
-                                          dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream()), "mft_ridge_backward_query")
-    _lib.check(h.mft_ridge_backward_support(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["L"]), _p(tape["alpha"]),
-                                            _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream()),
-               "mft_ridge_backward_support")
+    ld = feats.stride(0)
+    _lib.call("mft_ridge_backward_query", _p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
+              dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream())
+    _lib.call("mft_ridge_backward_support", _p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["L"]), _p(tape["alpha"]),
+              _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream())
     return dfeats, dscale
 
 
@@ -1387,7 +1345,7 @@ svm_check = ridge_check             # the SVM launchers' domain is the ridge hea
 def _svm_gram(feats, E, n_way, n_support, n_query):
     S = n_way * n_support
     M = torch.empty((E, S, S), device=feats.device, dtype=torch.float64)
-    _lib.check(_lib.lib().mft_svm_gram(_p(feats), feats.stride(0), E, n_way, n_support, n_query, RIDGE_D, _p(M), _stream()), "mft_svm_gram")
+    _lib.call("mft_svm_gram", _p(feats), feats.stride(0), E, n_way, n_support, n_query, RIDGE_D, _p(M), _stream())
     return M
 
 
@@ -1407,11 +1365,11 @@ def svm_forward(feats, scale, episodes, n_way, n_support, n_query, softmax=False
     status = torch.empty((E,), device=dev, dtype=torch.int32)
     work = torch.empty((E, _SVM_WORK), device=dev, dtype=torch.float64)
     M = _svm_gram(feats, E, n_way, n_support, n_query)
-    h, ld = _lib.lib(), feats.stride(0)
-    _lib.check(h.mft_svm_solve(_p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(work), _p(alpha), _p(free), _p(W), _p(status),
-                               _stream()), "mft_svm_solve")
-    _lib.check(h.mft_ridge_scores(_p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
-                                  _stream()), "mft_ridge_scores")
+    ld = feats.stride(0)
+    _lib.call("mft_svm_solve", _p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(work), _p(alpha), _p(free), _p(W), _p(status),
+              _stream())
+    _lib.call("mft_ridge_scores", _p(feats), ld, E, n_way, n_support, n_query, D, _p(W), _p(scale), _p(scores), 1 if softmax else 0,
+              _stream())
     products = work[:, 0]               # float64 [episodes]: products M x [S, n_way] the solve used
     if not save:
         return scores, dict(status=status, products=products)
@@ -1436,10 +1394,9 @@ def svm_backward(tape, dscores):
     dfeats, dW, dscale = new(feats.shape[0], D), new(E, n_way, D), new(1)
     part = torch.empty(E * 8, device=feats.device, dtype=torch.float64)
     M = _svm_gram(feats, E, n_way, n_support, n_query)
-    h, ld = _lib.lib(), feats.stride(0)
-    _lib.check(h.mft_ridge_backward_query(_p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
-                                          dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream()), "mft_ridge_backward_query")
-    _lib.check(h.mft_svm_backward_support(_p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(tape["alpha"]), _p(tape["free"]),
-                                          _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream()),
-               "mft_svm_backward_support")
+    ld = feats.stride(0)
+    _lib.call("mft_ridge_backward_query", _p(feats), ld, E, n_way, n_support, n_query, D, _p(tape["W"]), _p(scale), _p(dscores),
+              dscores.stride(0), _p(dfeats), D, _p(dW), _p(part), _stream())
+    _lib.call("mft_svm_backward_support", _p(feats), ld, E, n_way, n_support, n_query, D, _p(M), _p(tape["alpha"]), _p(tape["free"]),
+              _p(tape["W"]), _p(dW), _p(part), _p(dfeats), D, _p(dscale), _stream())
     return dfeats, dscale

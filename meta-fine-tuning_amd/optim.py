@@ -57,9 +57,8 @@ class Adam(torch.optim.Optimizer):
                 if cached is None or cached[0] != key:
                     cached = tables[id(group)] = (key, torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(ps[0].device))
                 table = cached[1]
-                rc = ops._lib.lib().mft_adam_multi(ops._p(table), len(rows), step, group["lr"], b1, b2, group["eps"],
-                                                   group["weight_decay"], float(self.grad_scale), ops._stream())
-                ops._lib.check(rc, "mft_adam_multi")
+                ops._lib.call("mft_adam_multi", ops._p(table), len(rows), step, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                              float(self.grad_scale), ops._stream())
             else:
                 for p in ps:
                     st = self.state[p]

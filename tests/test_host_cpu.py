@@ -1,8 +1,10 @@
 """CPU-only checks: the C-ABI library loads and exports every symbol include/mft_hip.h declares, the host
 mirrors keep the reference's state_dict / flag / sampling contracts, and the product path refuses to run
 without a GPU (no silent fallback)."""
+import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -28,6 +30,119 @@ def test_library_exports_every_declared_symbol():
     assert not [n for n in declared if n.startswith("mft_debug_") or n.endswith(("_set_exact", "_set_xcd"))]
     hooks = set(re.findall(r"\b(mft_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "mft_hip_testing.h")).read()))
     assert hooks == set(_lib.TESTING_SIGNATURES) and all(hasattr(h, n) for n in hooks)
+
+
+_JOB_STRUCTS = ("MftWgradJob", "MftBnStatsJob", "MftBnFwdJob", "MftBnApplyJob", "MftBnBwdJob", "MftFwtJob", "MftFwtGradJob")
+
+
+def test_binding_is_derived_from_the_header():
+    """One pinned launcher per type class of the header: the table is parsed from it, never typed by hand."""
+    P, I, L, U, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_float
+    S, R = _lib.SIGNATURES, _lib.RESTYPES
+    assert S["mft_fwt_draw_fold"][4] is U and S["mft_fwt_draw_fold"] == [P, I, I, I, U, P, P, P, P, P]
+    assert S["mft_gather_rows"] == [P, P, P, I, L, P]
+    assert S["mft_adam_step"].count(F) == 5 and S["mft_adam_step"] == [P, P, P, P, L, I, F, F, F, F, F, P]
+    ws_floats = [n for n in S if n.endswith("_ws_floats")]
+    assert ws_floats and all(R[n] is L for n in ws_floats)
+    assert S["mft_version"] == [] and R["mft_version"] is I
+    assert _lib.TESTING_SIGNATURES["mft_wgrad_fwd_set_exact"] == [I] and _lib.TESTING_SIGNATURES["mft_wgrad_fwd_set_xcd"] == [I]
+    assert R["mft_wgrad_fwd_set_exact"] is None and R["mft_wgrad_fwd_set_xcd"] is None
+    assert set(R) == set(S) | set(_lib.TESTING_SIGNATURES)
+    h = _lib.lib()                                           # ... and it is what the loaded functions carry
+    for n in R:
+        assert getattr(h, n).restype is R[n] and list(getattr(h, n).argtypes or []) == {**S, **_lib.TESTING_SIGNATURES}[n], n
+    hdr = open(os.path.join(ROOT, "include", "mft_hip.h")).read()
+    assert int(re.search(r"#define\s+MFT_EINVAL\s+\((-?\d+)\)", hdr).group(1)) == _lib.MFT_EINVAL
+
+
+@pytest.mark.parametrize("text, what", [
+    ("int mft_a(const float* x, double y, void* stream);", "double y"),
+    ("int mft_a(const float* x, size_t n, void* stream);", "size_t n"),
+    ("double mft_a(void);", "double"),
+    ("int mft_a(int n);\nint mft_b(void);\nint mft_a(int n);", "mft_a is declared twice"),
+    ("typedef struct MftJob { const float* x; double eps; } MftJob;\nint mft_a(const MftJob* j);", "double eps"),
+    ("int mft_a(int n), mft_b(int n);", "not a prototype"),
+    ("", "no prototype"),
+    ("/* int mft_a(void); */\n#define MFT_X 1\n", "no prototype"),
+])
+def test_header_parser_refuses_to_guess(text, what):
+    with pytest.raises(RuntimeError) as e:
+        _lib.parse_header(text)
+    assert what in str(e.value)
+
+
+def test_header_parser_accepts_the_forms_the_headers_use():
+    protos, structs = _lib.parse_header("""
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        enum { MFT_A = 0, MFT_B = 1 };
+        typedef struct MftJob { const float* in; float* out; long long* count;   /* three pointers */
+                                int ld, C, rows; float eps, momentum; } MftJob;
+        long long mft_ws_floats(int C, long long rows);       // a count
+        void mft_set(int on);
+        int mft_go(const MftJob* jobs, const float* const* views, unsigned long long seed, unsigned* words, float eps,
+                   void* stream);
+        #ifdef __cplusplus
+        }
+        #endif""")
+    P, I, L, U, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_float
+    assert protos == {"mft_ws_floats": ([I, L], L), "mft_set": ([I], None), "mft_go": ([P, P, U, P, F, P], I)}
+    assert structs == {"MftJob": [("in", P), ("out", P), ("count", P), ("ld", I), ("C", I), ("rows", I), ("eps", F), ("momentum", F)]}
+
+
+def _host_clang():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    d = os.path.dirname(os.path.realpath(hipcc))
+    cands = [os.path.join(d, "amdclang"), os.path.join(d, "clang"), os.path.join(d, "..", "llvm", "bin", "clang"),
+             os.path.join(d, "..", "lib", "llvm", "bin", "clang")]
+    found = [c for c in cands if os.path.exists(c)]
+    assert found, "no host clang beside %s (looked at %s): the build needs one" % (hipcc, cands)
+    return found[0]
+
+
+def test_job_structs_match_the_compilers_layout(tmp_path):
+    """sizeof / offsetof of every job typedef as the host compiler lays include/mft_hip.h out == the ctypes classes _lib.struct builds."""
+    classes = {n: _lib.struct(n) for n in _JOB_STRUCTS}
+    assert _lib.struct("MftBnFwdJob") is classes["MftBnFwdJob"]                      # cached
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "mft_hip.h"', "int main(void) {"]
+    for n, c in classes.items():
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (n, n))
+        lines += ['  printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (n, f, n, f) for f, _ in c._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([_host_clang(), "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
+    want = {}
+    for n, c in classes.items():
+        want[n] = str(ctypes.sizeof(c))
+        want.update({"%s.%s" % (n, f): str(getattr(c, f).offset) for f, _ in c._fields_})
+    assert got == want
+    assert [f for f, _ in classes["MftFwtJob"]._fields_] == ["w", "b", "gamma", "beta", "w_fold", "b_fold", "gm", "C", "col"]
+
+
+def test_call_and_try_call(monkeypatch):
+    class Stub:
+        def __init__(self):
+            self.seen = []
+
+        def __getattr__(self, name):
+            def fn(*args):
+                self.seen.append((name, args))
+                return {"mft_ok": 0, "mft_refuses": _lib.MFT_EINVAL, "mft_fails": 719}[name]
+            return fn
+
+    stub = Stub()
+    monkeypatch.setattr(_lib, "_lib", stub)                  # what lib() hands out, as a running LaunchTimer does
+    assert _lib.call("mft_ok", 1, 2.5, None) is None and _lib.try_call("mft_ok", 3) is True
+    assert stub.seen == [("mft_ok", (1, 2.5, None)), ("mft_ok", (3,))]
+    with pytest.raises(RuntimeError, match=r"mft_refuses failed with code -22 "):
+        _lib.call("mft_refuses", 1)
+    assert _lib.try_call("mft_refuses", 1) is False
+    for f in (_lib.call, _lib.try_call):
+        with pytest.raises(RuntimeError, match=r"mft_fails failed with code 719 "):
+            f("mft_fails")
 
 
 def test_state_dict_contract():
