@@ -554,6 +554,41 @@ int mft_svm_backward_support(const float* feats, int ld, int episodes, int n_way
                              const double* M, const float* alpha, const unsigned char* free_mask, const float* W,
                              const float* dW, const double* dscale_part, float* dfeats, int ldd, float* dscale, void* stream);
 
+/* Transductive Propagation Network head (csrc/tpn.hip), every episode of a step per launch.  feats as for
+ * the ridge head (D = 512).  NODE n of an episode is support row n (class-major) for n < S = n_way * n_support and query row n - S
+ * (class-major) after that; N = n_way * (n_support + n_query) nodes.  u [episodes, N, D], W / mask / dd [episodes, N, N],
+ * F [episodes, N, n_way], rinv [episodes, N] and L [episodes, N (N + 1) / 2] (packed lower triangle, row after row) are in node
+ * order; hid [rows, 8], sig [rows] (float64) and dnode [rows, 9] (float64) are in the row order of feats.
+ *   embed:     hid = fc3 z (w3 [8, D], b3 [8]), sig = fc4 relu(hid) + EPS (w4 [8], b4 [1]; EPS = 2^-52), u = z / sig.
+ *   affinity:  W_ij = exp(-|u_i - u_j|^2 / 2) from direct differences; symmetric bit for bit, W_ii = 1.
+ *   propagate: one workgroup per episode.  Row i selects its min(k, N) largest entries (a tie goes to the lower column), or the
+ *              non-zero entries of row i of mask_in [episodes, N, N] when that is not NULL; mask = selection OR its transpose;
+ *              rinv = (sum_j (W mask)_ij + EPS)^-1/2; L = the Cholesky factor of I - alpha S, S = rinv (W mask) rinv;
+ *              F = (I - alpha S)^-1 Y, Y one-hot on the support nodes; scores [episodes * n_way * n_query, n_way] = the query
+ *              nodes of F.  L, F, mask and rinv are nullable (not saved).
+ *   propagate_backward: G = dscores (row stride ldg >= n_way) -> dd, the gradient with respect to the squared distances with the
+ *              two orders of every pair added (symmetric; the mask is a constant).
+ *   affinity_backward:  du_i = 2 sum_j dd_ij (u_i - u_j), then through u = z / sig and the two layers: EVERY row of dfeats
+ *              (row stride ldd >= D), dnode = d(loss) / d(hid) x 8 and d(loss) / d(sig) per row.
+ *   param_backward:     dw3 [8, D], db3 [8], dw4 [8], db4 [1], each summed over the rows in an order fixed by the row count.
+ * Storage fp32, sums in double inside the kernels, fixed summation order, no atomics, no data-dependent trip count.
+ * MFT_EINVAL outside n_way 1..32, N 1..256, n_support / n_query / episodes >= 1, k 1..256, D = 512, ld >= D a multiple of 4
+ * (ldd >= D), 16-byte aligned feats / w3 / u. */
+int mft_tpn_embed(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* w3,
+                  const float* b3, const float* w4, const float* b4, float* u, float* hid, double* sig, void* stream);
+int mft_tpn_affinity(int episodes, int n_way, int n_support, int n_query, int D, const float* u, float* W, void* stream);
+int mft_tpn_propagate(int episodes, int n_way, int n_support, int n_query, int D, const float* W, int k, float alpha,
+                      const unsigned char* mask_in, float* L, float* F, unsigned char* mask, float* rinv, float* scores,
+                      void* stream);
+int mft_tpn_propagate_backward(int episodes, int n_way, int n_support, int n_query, int D, const float* W, float alpha,
+                               const float* L, const float* F, const unsigned char* mask, const float* rinv, const float* dscores,
+                               int ldg, float* dd, void* stream);
+int mft_tpn_affinity_backward(int episodes, int n_way, int n_support, int n_query, int D, const float* u, const float* hid,
+                              const double* sig, const float* dd, const float* w3, const float* w4, float* dfeats, int ldd,
+                              double* dnode, void* stream);
+int mft_tpn_param_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* hid,
+                           const double* dnode, float* dw3, float* db3, float* dw4, float* db4, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

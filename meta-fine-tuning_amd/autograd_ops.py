@@ -586,6 +586,68 @@ def metaoptnet_svm_head(feats, scale, n_way, n_support, n_query, episodes=1):
     return scores
 
 
+class _TpnHeadFn(torch.autograd.Function):
+    """TPN head with a hand-written backward: ops.tpn_forward keeps the packed Cholesky factor, F, the
+    neighbour mask and D^-1/2, ops.tpn_backward returns the gradients of every feature row and of the four head parameters (the
+    mask is a constant of the backward)."""
+
+    @staticmethod
+    def forward(ctx, feats, w3, b3, w4, b4, n_way, n_support, n_query, episodes):
+        head = tuple(p.detach() for p in (w3, b3, w4, b4))
+        scores, tape = ops.tpn_forward(feats, head, episodes, n_way, n_support, n_query, save=True, mask=_TPN_FORCED[0])
+        ctx.save_for_backward(feats, *head)
+        ctx.tape = {k: v for k, v in tape.items() if k not in ("feats", "head")}
+        _TPN_LAST[0] = (tape["mask"], tape["W"])
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, *head = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.stride(1) == 1) else dscores.contiguous().float()
+        dfeats, dw3, db3, dw4, db4 = ops.tpn_backward(dict(ctx.tape, feats=feats, head=tuple(head)), d)
+        need = ctx.needs_input_grad
+        return (dfeats if need[0] else None, dw3 if need[1] else None, db3 if need[2] else None, dw4 if need[3] else None,
+                db4 if need[4] else None, None, None, None, None)
+
+
+_TPN_FORCED = [None]
+_TPN_LAST = [None]
+
+
+@contextlib.contextmanager
+def tpn_forced_graph(mask):
+    """Tests and golden parity only: inside the block every tpn_head call takes its neighbour selection from ``mask``
+    [episodes, N, N] (uint8, on the device; non-zero = selected) instead of the k largest entries per row."""
+    _TPN_FORCED[0] = mask
+    try:
+        yield mask
+    finally:
+        _TPN_FORCED[0] = None
+
+
+def tpn_last_graph():
+    """(mask [episodes, N, N] uint8, W [episodes, N, N]) of the last recorded tpn_head call, still on the device; None before it."""
+    return _TPN_LAST[0]
+
+
+def tpn_head(feats, fc3_w, fc3_b, fc4_w, fc4_b, n_way, n_support, n_query, episodes=1):
+    """TPN.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode
+    after the other), the four parameters of the relation module's fc3 / fc4 -> scores [episodes*n_way*n_query, n_way] = the query
+    rows of (I - alpha S)^-1 Y on the episode's k-nearest-neighbour graph.  Differentiable (features and the four parameters)
+    when autograd records; the no-grad path saves nothing."""
+    plist = (fc3_w, fc3_b, fc4_w, fc4_b)
+    _require_cuda(feats, "TPN head")
+    for p in plist:
+        _require_cuda(p, "TPN head")
+    ops.tpn_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in plist)):
+        return _TpnHeadFn.apply(feats, *plist, n_way, n_support, n_query, episodes)
+    return ops.tpn_forward(feats.detach(), tuple(p.detach() for p in plist), episodes, n_way, n_support, n_query,
+                           mask=_TPN_FORCED[0])[0]
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

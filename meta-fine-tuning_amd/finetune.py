@@ -176,6 +176,15 @@ def refuse_feature_wise_model(model_name, who):
                                   "backbone.plain_state_dict(state) dropped its gamma / beta keys" % who)
 
 
+def refuse_transductive(model=None, method=None, who="finetune"):
+    """TPN (methods/tpn.py) scores the queries of an episode together on a graph over support AND query nodes; the test-time engine
+    adapts on the support rows and scores each query on its own."""
+    from .train import TRANSDUCTIVE_METHODS
+    if method in TRANSDUCTIVE_METHODS or isinstance(model, tuple(TRANSDUCTIVE_METHODS.values())):
+        raise NotImplementedError("%s --method %s: the test-time engine has no transductive mode; score the method with `test` "
+                                  "(save_features, then test --method %s)" % ((who,) + 2 * (method or model.METHOD,)))
+
+
 def _params_of(p):
     if p is not None:
         refuse_feature_wise_model(p.model, "finetune")
@@ -197,6 +206,7 @@ def _finetune(P, liz_x, y, model, state_in, save_it, linear=False, flatten=True,
     if linear or not flatten or ds:
         raise NotImplementedError("finetune(): only the GNN scoring branch with a flattened backbone is on the HIP hot path "
                                   "(the linear branch is finetune_linear(); ds = DampNet, out of scope)")
+    refuse_transductive(model)
     P = _params_of(P)
     ready = _take_ready(liz_x, "gnn", freeze_backbone, state_in, model)
     if ready is not None:
@@ -319,6 +329,7 @@ def finetune_batched(episodes, model, state_in, fine_tune_epoch, n_way=5, n_supp
                      perms=None):
     """Throughput path: ``episodes`` (list of liz_x) processed ``episodes_per_batch`` at a time in lockstep.
     Permutations are drawn episode by episode from the global numpy RNG (the reference's order) unless given."""
+    refuse_transductive(model, who="finetune_batched")
     model = model.cuda()
     x0 = episodes[0][0]
     n_query = x0.size(1) - n_support
@@ -609,6 +620,7 @@ def evaluate(model, state, n_episodes, n_way, n_shot, n_query, size, gen_example
     ``emulate_world`` = (r, W) (measurement aid, single process only): run exactly rank r's share of a W-rank job -- the same
     episodes, seeds, batch sizes and engine as that rank would -- and return ITS accuracies only (no gather)."""
     import time
+    refuse_transductive(model, method, who="finetune.evaluate")
     t_start = time.perf_counter()
     rank, W = parallel.world()
     if emulate_world is not None:
@@ -916,6 +928,7 @@ def main(argv=None, model_cls=None, n_episodes=600, episodes_per_batch=None):
     rank, _W = parallel.world()
     from .methods.gnnnet import GnnNet
     from .methods import gnnnet_copy
+    refuse_transductive(method=params.method, who="finetune.main")
     if params.method not in ('gnnnet', 'baseline', 'baseline++', 'all'):
         raise NotImplementedError("--method %s: 'gnnnet', 'baseline', 'baseline++' and 'all' are on the HIP hot path (protonet / "
                                   "relationnet / dampnet are out of scope, SURVEY.md §2.1)" % params.method)

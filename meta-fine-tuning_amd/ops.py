@@ -1334,8 +1334,108 @@ def ridge_backward(tape, dscores):
     return dfeats, dscale
 
 
+# ---------------------------------------------------------------------------------------------- TPN head (csrc/tpn.hip)
+TPN_D, TPN_MAX_N, TPN_MAX_WAY = 512, 256, 32
+TPN_K, TPN_ALPHA = 20, 0.99
+
+
+def tpn_check(episodes, n_way, n_support, n_query, D=TPN_D, k=TPN_K):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != TPN_D:
+        raise ValueError("TPN head: feature dimension %d is not supported (D = %d)" % (D, TPN_D))
+    if not 1 <= int(n_way) <= TPN_MAX_WAY:
+        raise ValueError("TPN head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), TPN_MAX_WAY))
+    if int(n_support) < 1 or int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("TPN head: n_support = %d, n_query = %d, episodes = %d (all must be >= 1)"
+                         % (int(n_support), int(n_query), int(episodes)))
+    if int(n_way) * (int(n_support) + int(n_query)) > TPN_MAX_N:
+        raise ValueError("TPN head: N = n_way * (n_support + n_query) = %d nodes is not supported (N <= %d: the factor of one "
+                         "episode's graph is kept in one workgroup's LDS)" % (int(n_way) * (int(n_support) + int(n_query)), TPN_MAX_N))
+    if not 1 <= int(k) <= TPN_MAX_N:
+        raise ValueError("TPN head: k = %d neighbours is not supported (1 <= k <= %d)" % (int(k), TPN_MAX_N))
+
+
+def _tpn_head(head):
+    w3, b3, w4, b4 = head
+    for t, shape in ((w3, (8, TPN_D)), (b3, (8,)), (w4, (1, 8)), (b4, (1,))):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("TPN head: fc3 / fc4 must be float32 tensors on the GPU (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError("TPN head: expected contiguous float32 fc3.weight [8, %d], fc3.bias [8], fc4.weight [1, 8], fc4.bias [1]; "
+                               "got %s %s" % (TPN_D, t.dtype, tuple(t.shape)))
+    return w3, b3, w4, b4
+
+
+def tpn_forward(feats, head, episodes, n_way, n_support, n_query, k=TPN_K, alpha=TPN_ALPHA, save=False, mask=None):
+    """TPN head forward: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode after
+    the other, row stride >= 512), head = (fc3.weight, fc3.bias, fc4.weight, fc4.bias) on the device -> (scores
+    [episodes*n_way*n_query, n_way], tape | None).  Three launches whatever the shape: embed, affinity, propagate.  ``save``: keep
+    what tpn_backward needs; the tape also exposes ``W`` [episodes, N, N] and ``mask`` [episodes, N, N] (uint8).  ``mask``
+    [episodes, N, N] (tests and golden parity only): the neighbour selection instead of the k largest entries per row."""
+    if not feats.is_cuda:
+        raise RuntimeError("TPN head: input is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % feats.device)
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("TPN head: expected float32 rows [R, D] with unit column stride, got %s %s" % (feats.dtype, tuple(feats.shape)))
+    tpn_check(episodes, n_way, n_support, n_query, feats.shape[1], k)
+    E, D, N, Q = episodes, TPN_D, n_way * (n_support + n_query), n_way * n_query
+    if feats.shape[0] != E * N:
+        raise ValueError("TPN head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]" % (tuple(feats.shape), E * N, D))
+    if feats.stride(0) < D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("TPN head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), D))
+    w3, b3, w4, b4 = _tpn_head(head)
+    if mask is not None:
+        if not mask.is_cuda:
+            raise RuntimeError("TPN head: the forced mask is on %s -- the MI355X path has no CPU fallback" % mask.device)
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != E * N * N:
+            raise ValueError("TPN head: the forced mask must be a contiguous uint8 tensor [episodes, N, N] = [%d, %d, %d]" % (E, N, N))
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    u, hid, W, scores = new(E * N, D), new(E * N, 8), new(E, N, N), new(E * Q, n_way)
+    sig = torch.empty(E * N, device=dev, dtype=torch.float64)
+    L = F = mk = rinv = None
+    if save:
+        L, F, rinv = new(E, N * (N + 1) // 2), new(E, N, n_way), new(E, N)
+        mk = torch.empty((E, N, N), device=dev, dtype=torch.uint8)
+    _lib.call("mft_tpn_embed", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(w3), _p(b3), _p(w4), _p(b4), _p(u),
+              _p(hid), _p(sig), _stream())
+    _lib.call("mft_tpn_affinity", E, n_way, n_support, n_query, D, _p(u), _p(W), _stream())
+    _lib.call("mft_tpn_propagate", E, n_way, n_support, n_query, D, _p(W), int(k), float(alpha), _p(mask), _p(L), _p(F), _p(mk),
+              _p(rinv), _p(scores), _stream())
+    if not save:
+        return scores, None
+    return scores, dict(feats=feats, head=(w3, b3, w4, b4), u=u, hid=hid, sig=sig, W=W, L=L, F=F, mask=mk, rinv=rinv, alpha=float(alpha),
+                        shape=(E, n_way, n_support, n_query))
+
+
+def tpn_backward(tape, dscores):
+    """d(scores) [episodes*n_way*n_query, n_way] -> (dfeats [rows, 512] with every row written, dW3 [8, 512], db3 [8], dW4 [1, 8],
+    db4 [1]) from the forward's tape.  Three launches whatever the shape: propagate backward, affinity backward, the parameter
+    sums."""
+    E, n_way, n_support, n_query = tape["shape"]
+    feats = tape["feats"]
+    w3, b3, w4, b4 = tape["head"]
+    D, N, Q = TPN_D, n_way * (n_support + n_query), n_way * n_query
+    if not dscores.is_cuda:
+        raise RuntimeError("TPN head: d(scores) is on %s -- the MI355X path has no CPU fallback" % dscores.device)
+    if dscores.dtype != torch.float32 or dscores.dim() != 2 or dscores.stride(1) != 1:
+        raise RuntimeError("TPN head: expected float32 d(scores) with unit column stride")
+    if tuple(dscores.shape) != (E * Q, n_way):
+        raise ValueError("tpn_backward: dscores is %s, expected [%d, %d]" % (tuple(dscores.shape), E * Q, n_way))
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    dd, dfeats, dw3, db3, dw4, db4 = new(E, N, N), new(E * N, D), new(8, D), new(8), new(1, 8), new(1)
+    dnode = torch.empty((E * N, 9), device=dev, dtype=torch.float64)
+    _lib.call("mft_tpn_propagate_backward", E, n_way, n_support, n_query, D, _p(tape["W"]), tape["alpha"], _p(tape["L"]), _p(tape["F"]),
+              _p(tape["mask"]), _p(tape["rinv"]), _p(dscores), dscores.stride(0), _p(dd), _stream())
+    _lib.call("mft_tpn_affinity_backward", E, n_way, n_support, n_query, D, _p(tape["u"]), _p(tape["hid"]), _p(tape["sig"]), _p(dd),
+              _p(w3), _p(w4), _p(dfeats), D, _p(dnode), _stream())
+    _lib.call("mft_tpn_param_backward", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(tape["hid"]), _p(dnode),
+              _p(dw3), _p(db3), _p(dw4), _p(db4), _stream())
+    return dfeats, dw3, db3, dw4, db4
+
+
 # ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
-SVM_C = 0.1                         # the published C_reg; a constant of the kernels
+SVM_C = 0.1                        # the published C_reg; a constant of the kernels
 SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1
 _SVM_WORK = 1024 * 16               # float64 workspace of mft_svm_solve per episode
 

@@ -15,7 +15,7 @@ from .data.feature_loader import save_features_file
 from .io_utils import get_assigned_file, get_best_file, get_resume_file, method_dir_name, model_dict, parse_args
 
 BASELINES = ('baseline', 'baseline++')
-METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet')
+METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn')
 SPLIT_SEEDS = {'base': 0, 'val': 2, 'novel': 3}       # miniImageNet-shaped pool per --split; 'base' is train.main's pool (seed 0)
 TEST_DATASET_SEED = 1                                 # --test_dataset X: the pool finetune.main evaluates on
 CHUNK = 200                                           # images per backbone forward
@@ -57,10 +57,12 @@ def resolve_state(p, verbose=True):
     puts the deterministic stand-in weights in its place) -> (state, file | None)."""
     from .finetune import _resolve_state
     state, loaded = _resolve_state(p.method, checkpoint_file(p), p.test_n_way, p.save_iter != -1, verbose)
-    if loaded is None and p.method in ('protonet', 'matchingnet', 'metaoptnet'):
+    from .train import head_method
+    if loaded is None and head_method(p.method) is not None:
         # the stand-in is a GnnNet state: keep its backbone, put the method's own seeded head behind it
         state = type(state)((k, v) for k, v in state.items() if k.startswith("feature."))
-        state.update({'matchingnet': synthetic.matchingnet_head_state, 'metaoptnet': synthetic.metaoptnet_head_state}.get(p.method, dict)())
+        state.update({'matchingnet': synthetic.matchingnet_head_state, 'metaoptnet': synthetic.metaoptnet_head_state,
+                      'tpn': synthetic.tpn_head_state}.get(p.method, dict)())
     return state, loaded
 
 

@@ -158,6 +158,20 @@ def metaoptnet_head_state(seed=27):
     return OrderedDict([("scale", torch.tensor([v], dtype=torch.float32))])
 
 
+def tpn_head_state(seed=30, dim=512):
+    """The four TPN head tensors, state-dict keys and order of methods.tpn.TPN after ``feature.*``:
+    ``relation.fc3.weight`` ~ 0.02 N(0,1), ``relation.fc3.bias`` ~ 0.1 N(0,1), ``relation.fc4.weight`` ~ 0.3 N(0,1) and
+    ``relation.fc4.bias`` = 12, the constructor's value: sigma stays near 12 and the kept affinities are neither 0 nor 1."""
+    rs = np.random.RandomState(seed)
+    f32 = lambda a: torch.from_numpy(a.astype(np.float32))  # noqa: E731
+    sd = OrderedDict()
+    sd["relation.fc3.weight"] = f32(0.02 * rs.standard_normal((8, dim)))
+    sd["relation.fc3.bias"] = f32(0.1 * rs.standard_normal(8))
+    sd["relation.fc4.weight"] = f32(0.3 * rs.standard_normal((1, 8)))
+    sd["relation.fc4.bias"] = torch.full((1,), 12.0, dtype=torch.float32)
+    return sd
+
+
 def _templates(rs, n_way, size):
     """Per-class low-frequency templates: 7x7 gaussian grids upsampled bilinearly."""
     low = torch.from_numpy(rs.standard_normal((n_way, 3, 7, 7)).astype(np.float32))

@@ -1,4 +1,4 @@
-"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / baseline / baseline++): Adam over all parameters, 100
+"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / tpn / baseline / baseline++): Adam over all parameters, 100
 episodes per epoch, checkpoints ``{'epoch','state'}`` under <save_dir>/checkpoints/<dataset>/<model>_<method>
 [_aug]_<n>way_<k>shot/<epoch>.tar, optional first-order-MAML meta-fine-tuning (--fine_tune).
 The episode source is the in-repo synthetic miniImageNet-shaped sampler (real data is out of scope)."""
@@ -14,8 +14,15 @@ from .methods.gnnnet import GnnNet
 from .methods.matchingnet import MatchingNet
 from .methods.metaoptnet import MetaOptNet
 from .methods.protonet import ProtoNet
+from .methods.tpn import TPN
 
 HEAD_METHODS = {'protonet': ProtoNet, 'matchingnet': MatchingNet, 'metaoptnet': MetaOptNet}      # --method -> class (train.py:138-139)
+TRANSDUCTIVE_METHODS = {'tpn': TPN}     # HeadMethods that score an episode's queries together: trained and scored by `test`, no test-time engine mode
+
+
+def head_method(name):
+    """The HeadMethod class of ``--method name`` over both tables, or None."""
+    return HEAD_METHODS.get(name) or TRANSDUCTIVE_METHODS.get(name)
 
 
 class SyntheticEpisodeLoader:
@@ -190,11 +197,11 @@ def train(base_loader, model, optimization, start_epoch, stop_epoch, params, var
         if params.method in ('baseline', 'baseline++'):
             model.train_loop(epoch, base_loader, optimizer)              # train.py:41-42: every other method -> train_loop
         elif not params.fine_tune and getattr(params, "episodes_per_rank", 1) > 1:
-            if fifty and params.method not in HEAD_METHODS:
+            if fifty and head_method(params.method) is None:
                 raise NotImplementedError("--episodes_per_rank with the 50-shot loops")
             model.train_loop_lockstep(epoch, base_loader, optimizer, params.episodes_per_rank)
         elif not params.fine_tune:
-            if params.method in HEAD_METHODS:
+            if head_method(params.method) is not None:
                 model.train_loop(epoch, base_loader, optimizer)          # train.py:48-49 / train_50.py:48-49: the else branch
             else:
                 (model.train_loop50 if fifty else model.train_loop2)(epoch, base_loader, optimizer)
@@ -226,12 +233,12 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     rank, W = parallel.world()
     if not params.start_epoch > 0:
         np.random.seed(10)
-    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'baseline' and 'baseline++' are on the HIP path"
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet', 'tpn'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'baseline' and 'baseline++' are on the HIP path"
                                   % params.method)
-    if params.method in HEAD_METHODS and params.fine_tune:
+    if head_method(params.method) is not None and params.fine_tune:
         raise NotImplementedError("--method %s --fine_tune: %s's first-order-MAML meta-training is not on the HIP path"
-                                  % (params.method, HEAD_METHODS[params.method].__name__))
+                                  % (params.method, head_method(params.method).__name__))
     if params.model == 'ResNet10_FW' and params.fine_tune:
         raise NotImplementedError("--model ResNet10_FW --fine_tune: the reference keeps the feature-wise noise on inside the inner loop, "
                                   "and the fused inner-loop kernels have no per-episode affine; meta-train ResNet10_FW without --fine_tune")
@@ -254,8 +261,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
                                                 aug=params.train_aug, rank=rank, world=W)
         else:
             base_loader = SyntheticEpisodeLoader(params.train_n_way, params.n_shot, n_query, size, n_episode, rank=rank, world=W)
-        if params.method in HEAD_METHODS:
-            cls = HEAD_METHODS[params.method]
+        if head_method(params.method) is not None:
+            cls = head_method(params.method)
         else:
             cls = gnnnet_copy.GnnNet if (variant50 and params.n_shot == 50) else GnnNet          # train_50.py:154-157
         torch.manual_seed(0) if W > 1 else None
