@@ -577,9 +577,13 @@ __global__ __launch_bounds__(256) void graph_aggregate_bwd_kernel(const float* _
     const long long b = row / N;
     const int i = (int)(row % N);
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
-        float s = dy[row * lddy + f];
+        // the N terms of A^T dy (each a fraction of a gradient: softmax rows sum to 1) are summed among themselves and the node's
+        // own gradient is added last -- started from dy[row][f], every one of the N additions rounds at the size of the LARGE term
+        // (N = 65 / 130: 5-8 float32 roundings of it, tests/test_gnn_backward_gpu.py)
+        float s = 0.f;
 #pragma unroll 10
-        for (int j = 0; j < N; ++j) s += A[(b * N + j) * N + i] * dy[(b * N + j) * lddy + F + f];      // (ten loads in flight; same order)
+        for (int j = 0; j < N; ++j) s += A[(b * N + j) * N + i] * dy[(b * N + j) * lddy + F + f];      // (ten loads in flight; j ascending)
+        s += dy[row * lddy + f];
         dx[row * lddx + f] = accumulate ? dx[row * lddx + f] + s : s;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
