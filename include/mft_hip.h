@@ -589,6 +589,76 @@ int mft_tpn_affinity_backward(int episodes, int n_way, int n_support, int n_quer
 int mft_tpn_param_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* hid,
                            const double* dnode, float* dw3, float* db3, float* dw4, float* db4, void* stream);
 
+/* FEAT head: embedding adaptation with a set-to-set function (csrc/feat.hip), every set of every episode of a
+ * step per launch.  feats as for mft_proto_scores with D = 512 and T = n_support + n_query rows per class.
+ *
+ * TOKENS.  X [Ntok, D]: rows 0 .. NP - 1 (NP = episodes * n_way) are the prototypes, one set of n_way tokens per episode; with
+ * train != 0 the NA = episodes * n_way * T rows behind them are the feature rows themselves, one set of T tokens per class (support
+ * rows first).  Ntok = NP + (train ? NA : 0).  qkv / dqkv are [3, Ntok, D]; o, y, A, dA, dy, dXres, dX are [Ntok, D]; mean / rstd
+ * [Ntok].  P, dS and the multiplier m_att hold one [t, t] block per set, the episodes' [n_way, n_way] blocks first and then the
+ * classes' [T, T] blocks; the multiplier m_out is [Ntok, D].  A NULL multiplier is 1.
+ *   tokens:    the prototypes (support rows summed in row order, / n_support) and, in train mode, the copy of the rows.
+ *   project:   qkv[z] = X Wz^T (z = q, k, v).          fc: y = o Wfc^T + b_fc.
+ *   attention: P = softmax_rows(q k^T / sqrt(D)) with the maximum subtracted, saved before the multiplier; o = (m_att P) v.
+ *              A set of one token gives o = v bit for bit.
+ *   norm:      h = m_out y + X, A = LayerNorm(h) ln_w + ln_b over D (biased variance, eps 1e-5); saves mean and rstd.
+ *   scores:    scores[q, c] = -|z_q - A_c|^2 / temperature on the prototype tokens; in train mode centre [NP, D] = the mean over the
+ *              T tokens of each class's set and reg[r, c] = -|z_r - centre_c|^2 / temperature2 for every feature row r.
+ *   loss:      out[0] = CE(scores) + balance CE(reg), out[1] = CE(scores), out[2] = CE(reg) (means; the label of a row is its
+ *              class; reg NULL: the main term alone); *loss_sum (nullable) += out[1].  loss_backward: dscores and dreg of
+ *              out[0] * grad_loss[0] (device scalar; NULL = 1).
+ *   scores_backward: ddirect [rows, D] = the gradient of every feature row through the distances (zero where there is none) and
+ *              dA (prototype tokens; in train mode every class token gets dcentre / T).
+ *   norm_backward:   dy = m_out dh, dXres = dh, and the column sums dln_w, dln_b, db_fc over the Ntok rows in an order that
+ *              depends on Ntok alone.        fc_backward: do = dy Wfc, dWfc = dy^T o.
+ *   attention_backward: dqkv from do, the saved P and the same multiplier (dS is workspace).
+ *   project_backward:   dX = dXres + sum_z dqkv[z] Wz, dW [3, D, D] = dqkv[z]^T X.
+ *   dfeats:    EVERY row of dfeats (row stride ldd) once: ddirect, plus dX of the class's prototype / n_support for a support row,
+ *              plus in train mode dX of the row's own token.
+ *   draw:      m_att and m_out of a train-mode step, each 0 or 1 / (1 - p), from Philox4x32-10 (csrc/philox.h): element i of
+ *              mask id b (0 = m_att, 1 = m_out) takes word 0 of counter (i low, i high | b << 31, index low, index high), key =
+ *              seed, and is kept iff word * 2^-32 >= p.  The draw index is read from device memory and index + 1 is stored by the
+ *              launch (one workgroup, as mft_fwt_draw_fold), so a replayed hipGraph draws fresh masks.  in_att / in_out (both or
+ *              neither) replace the draw: the test hook.
+ * Storage fp32; every sum, the exponential and the normalisations run in double and round once on the store; no atomics, fixed
+ * summation order, no data-dependent trip count; an episode's result does not depend on its neighbours.
+ * MFT_EINVAL outside episodes >= 1, n_way 1..32, n_support >= 1, n_query >= 1, T <= 128, D = 512, ld >= D a multiple of 4
+ * (ldd too), 16-byte aligned feats / dfeats, Ntok * D and the P blocks below 2^31 elements.  T <= 128 because one wave holds a
+ * softmax row, two entries per lane; 5-way 50-shot with 16 queries is T = 66. */
+int mft_feat_tokens(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int train, float* X,
+                    void* stream);
+int mft_feat_project(const float* X, int episodes, int n_way, int n_support, int n_query, int D, int train, const float* wq,
+                     const float* wk, const float* wv, float* qkv, void* stream);
+int mft_feat_attention(const float* qkv, int episodes, int n_way, int n_support, int n_query, int D, int train, const float* m_att,
+                       float* P, float* o, void* stream);
+int mft_feat_fc(const float* o, int episodes, int n_way, int n_support, int n_query, int D, int train, const float* wfc,
+                const float* bfc, float* y, void* stream);
+int mft_feat_norm(const float* y, const float* X, int episodes, int n_way, int n_support, int n_query, int D, int train,
+                  const float* m_out, const float* ln_w, const float* ln_b, float* A, float* mean, float* rstd, void* stream);
+int mft_feat_scores(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int train, const float* A,
+                    float temperature, float temperature2, float* scores, float* centre, float* reg, void* stream);
+int mft_feat_loss(const float* scores, const float* reg, int episodes, int n_way, int n_support, int n_query, float balance,
+                  float* out, double* loss_sum, void* stream);
+int mft_feat_loss_backward(const float* scores, const float* reg, int episodes, int n_way, int n_support, int n_query, float balance,
+                           const float* grad_loss, float* dscores, float* dreg, void* stream);
+int mft_feat_scores_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int train,
+                             const float* A, const float* centre, const float* dscores, const float* dreg, float temperature,
+                             float temperature2, float* ddirect, float* dA, void* stream);
+int mft_feat_norm_backward(const float* dA, const float* y, const float* X, int episodes, int n_way, int n_support, int n_query, int D,
+                           int train, const float* m_out, const float* ln_w, const float* mean, const float* rstd, float* dy,
+                           float* dXres, float* dln_w, float* dln_b, float* dbfc, void* stream);
+int mft_feat_fc_backward(const float* dy, const float* o, int episodes, int n_way, int n_support, int n_query, int D, int train,
+                         const float* wfc, float* d_o, float* dwfc, void* stream);
+int mft_feat_attention_backward(const float* d_o, const float* qkv, const float* P, const float* m_att, int episodes, int n_way,
+                                int n_support, int n_query, int D, int train, float* dS, float* dqkv, void* stream);
+int mft_feat_project_backward(const float* dqkv, const float* X, const float* dXres, int episodes, int n_way, int n_support,
+                              int n_query, int D, int train, const float* wq, const float* wk, const float* wv, float* dX, float* dW,
+                              void* stream);
+int mft_feat_dfeats(const float* ddirect, const float* dX, int episodes, int n_way, int n_support, int n_query, int D, int train,
+                    float* dfeats, int ldd, void* stream);
+int mft_feat_draw(int episodes, int n_way, int n_support, int n_query, int D, float p_att, float p_out, unsigned long long seed,
+                  unsigned long long* index, const float* in_att, const float* in_out, float* m_att, float* m_out, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

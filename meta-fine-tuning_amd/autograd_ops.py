@@ -648,6 +648,106 @@ def tpn_head(feats, fc3_w, fc3_b, fc4_w, fc4_b, n_way, n_support, n_query, episo
                            mask=_TPN_FORCED[0])[0]
 
 
+class _FeatHeadFn(torch.autograd.Function):
+    """FEAT head with a hand-written backward: ops.feat_forward keeps the tokens, the projections, the
+    attention rows before dropout and the LayerNorm statistics; ops.feat_backward returns the gradients of every feature row and of
+    the seven head parameters.  Train mode returns (scores, reg), eval mode scores alone."""
+
+    @staticmethod
+    def forward(ctx, feats, wq, wk, wv, ln_w, ln_b, wfc, bfc, n_way, n_support, n_query, episodes, train, masks, temps):
+        head = tuple(p.detach() for p in (wq, wk, wv, ln_w, ln_b, wfc, bfc))
+        scores, reg, tape = ops.feat_forward(feats, head, episodes, n_way, n_support, n_query, train, masks=masks, save=True,
+                                             temperature=temps[0], temperature2=temps[1])
+        ctx.save_for_backward(feats, *head)
+        ctx.tape = {k: v for k, v in tape.items() if k not in ("feats", "head")}
+        ctx.set_materialize_grads(False)                 # an unused output's gradient stays None: no fill launch
+        return (scores, reg) if train else scores
+
+    @staticmethod
+    def backward(ctx, dscores, dreg=None):
+        feats, *head = ctx.saved_tensors
+        fix = lambda d: d if (d is None or (d.dtype == torch.float32 and d.is_contiguous())) else d.contiguous().float()  # noqa: E731
+        if dscores is None:
+            dscores = torch.zeros((ctx.tape["shape"][0] * ctx.tape["shape"][1] * ctx.tape["shape"][3], ctx.tape["shape"][1]),
+                                  device=feats.device, dtype=torch.float32)
+        grads = ops.feat_backward(dict(ctx.tape, feats=feats, head=tuple(head)), fix(dscores), fix(dreg))
+        need = ctx.needs_input_grad
+        return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 7
+
+
+_FEAT_FORCED = [None]
+
+
+@contextlib.contextmanager
+def feat_forced_masks(masks):
+    """Tests and golden parity only: inside the block every train-mode FEAT head call takes its dropout multipliers (m_att, m_out)
+    from ``masks`` (float32, on the device, the layout of ops.feat_draw) instead of the generator."""
+    _FEAT_FORCED[0] = masks
+    try:
+        yield masks
+    finally:
+        _FEAT_FORCED[0] = None
+
+
+def feat_forced():
+    return _FEAT_FORCED[0]
+
+
+def feat_head(feats, head, n_way, n_support, n_query, episodes=1, train=False, masks=None,
+              temperature=ops.FEAT_TEMPERATURE, temperature2=ops.FEAT_TEMPERATURE2):
+    """FEAT.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode
+    after the other), the seven slf_attn parameters in state-dict order -> scores [episodes*n_way*n_query, n_way]; ``train``:
+    (scores, reg [rows, n_way]) with the auxiliary sets, ``masks`` = (m_att, m_out) their dropout multipliers (None: 1).
+    Differentiable (features and the seven parameters) when autograd records; the no-grad path saves nothing."""
+    plist = tuple(head)
+    _require_cuda(feats, "FEAT head")
+    for p in plist:
+        _require_cuda(p, "FEAT head")
+    ops.feat_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    temps = (float(temperature), float(temperature2))
+    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in plist)):
+        return _FeatHeadFn.apply(feats, *plist, n_way, n_support, n_query, episodes, bool(train), masks, temps)
+    scores, reg, _ = ops.feat_forward(feats.detach(), tuple(p.detach() for p in plist), episodes, n_way, n_support, n_query, train,
+                                      masks=masks, temperature=temps[0], temperature2=temps[1])
+    return (scores, reg) if train else scores
+
+
+class _FeatLossFn(torch.autograd.Function):
+    """CE(scores) + balance CE(reg) (means; a row's label is its class) with ONE launch each way (mft_feat_loss / _backward).
+    Returns the 0-dim tensors (total, main term, auxiliary term); only the total is differentiable."""
+
+    @staticmethod
+    def forward(ctx, scores, reg, shape, balance, loss_sum):
+        out = ops.feat_loss(scores, reg, *shape, balance=balance, loss_sum=loss_sum)
+        ctx.save_for_backward(scores, reg)
+        ctx.shape, ctx.balance = shape, balance
+        total, main, aux = out[0], out[1], out[2]        # views of the launch's output: no device work
+        ctx.mark_non_differentiable(main, aux)
+        ctx.set_materialize_grads(False)
+        return total, main, aux
+
+    @staticmethod
+    def backward(ctx, g, _gm=None, _ga=None):
+        scores, reg = ctx.saved_tensors
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+            g = g.reshape(-1)[:1].float()
+        dscores, dreg = ops.feat_loss_backward(scores, reg, *ctx.shape, g, balance=ctx.balance)
+        return dscores, dreg, None, None, None
+
+
+def feat_loss(scores, reg, episodes, n_way, n_support, n_query, balance=ops.FEAT_BALANCE, loss_sum=None):
+    """(loss, main, aux): loss = CE(scores, y_query) + balance CE(reg, y_all) as a 0-dim tensor (``reg`` None: the main term alone)
+    and its two terms (0-dim, not differentiable).  ``loss_sum`` (float64 device scalar) += the main term."""
+    _require_cuda(scores, "FEAT loss")
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        scores = scores.contiguous().float()
+    if reg is not None and (reg.dtype != torch.float32 or not reg.is_contiguous()):
+        reg = reg.contiguous().float()
+    return _FeatLossFn.apply(scores, reg, (episodes, n_way, n_support, n_query), float(balance), loss_sum)
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

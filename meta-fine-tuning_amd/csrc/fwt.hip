@@ -11,7 +11,7 @@
 // Words 0 and 1 of the output become two uniforms in (0, 1) and one Box-Muller pair, evaluated in double and rounded once.
 // The draw index is read by every thread, then -- behind a barrier -- advanced by thread 0: the launch is ONE workgroup (at most
 // 3,712 values per group), so nothing waits on another workgroup and a replayed hipGraph draws fresh noise every step.
-#include "mft_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -35,21 +35,6 @@ struct FwtUnfoldArgs {
     int n, groups, ld;
     const float* noise;
 };
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned& o0, unsigned& o1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o0 = c0;
-    o1 = c1;
-}
 
 // F.softplus(x, beta=100) with torch's threshold: x where 100 x > 20
 __device__ __forceinline__ float softplus100(float x) {

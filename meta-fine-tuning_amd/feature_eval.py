@@ -185,7 +185,7 @@ def build_model(method, model_func, n_way, n_support, head="ridge"):
     """The model `test` scores with: BaselineFinetune for the two baselines, GnnNet, or the method's class of train.HEAD_METHODS
     (``head``: MetaOptNet's, --head)."""
     from .io_utils import method_dir_name
-    from .train import HEAD_METHODS, TRANSDUCTIVE_METHODS, head_method
+    from .train import EMBEDDING_METHODS, HEAD_METHODS, TRANSDUCTIVE_METHODS, head_method
     method_dir_name(method, head)                         # a head that is unknown or not this method's is a ValueError
     if method == 'baseline':
         return BaselineFinetune(model_func, n_way, n_support)
@@ -197,4 +197,4 @@ def build_model(method, model_func, n_way, n_support, head="ridge"):
         kw = dict(head=head) if method == 'metaoptnet' else {}
         return head_method(method)(model_func, n_way=n_way, n_support=n_support, **kw)
     raise NotImplementedError("--method %s: 'baseline', 'baseline++', 'gnnnet', %s are on the HIP path"
-                              % (method, ", ".join(repr(m) for m in sorted(list(HEAD_METHODS) + list(TRANSDUCTIVE_METHODS)))))
+                              % (method, ", ".join(repr(m) for m in sorted(list(HEAD_METHODS) + list(TRANSDUCTIVE_METHODS) + list(EMBEDDING_METHODS)))))

@@ -29,7 +29,7 @@ _COMMON = [
     ("--test_dataset", dict(default="", help="test dataset")),
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
-    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/gnnnet/all")),
+    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/feat/gnnnet/all")),
     ("--head", dict(default="ridge", help="--method metaoptnet: its head, ridge (ridge regression) or svm")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),
     ("--test_n_way", dict(default=5, type=int, help="class num to classify for testing (validation)")),

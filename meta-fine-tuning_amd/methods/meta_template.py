@@ -96,9 +96,13 @@ class MetaTemplate(nn.Module):
             loss = loss_fn(x)
             loss.backward()
             optimizer.step()
-            avg_loss = avg_loss + loss.item()
+            avg_loss = avg_loss + self._loss_item(loss)
             if i % print_freq == 0:
                 print('Epoch {:d} | Batch {:d}/{:d} | Loss {:f}'.format(epoch, i, len(train_loader), avg_loss / float(i + 1)))
+
+    def _loss_item(self, loss):
+        """What the eager episode loop adds to its running loss (a method with an auxiliary term reports its main term)."""
+        return loss.item()
 
     def train_loop(self, epoch, train_loader, optimizer):
         self._episode_loop(epoch, train_loader, optimizer, self.set_forward_loss)

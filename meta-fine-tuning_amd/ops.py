@@ -1434,6 +1434,173 @@ def tpn_backward(tape, dscores):
     return dfeats, dw3, db3, dw4, db4
 
 
+# ---------------------------------------------------------------------------------------------- FEAT head (csrc/feat.hip)
+FEAT_D, FEAT_MAX_WAY, FEAT_MAX_T = 512, 32, 128
+FEAT_TEMPERATURE, FEAT_TEMPERATURE2, FEAT_BALANCE, FEAT_P_ATT, FEAT_P_OUT = 64.0, 32.0, 0.01, 0.1, 0.5
+FEAT_HEAD_SHAPES = ((FEAT_D, FEAT_D), (FEAT_D, FEAT_D), (FEAT_D, FEAT_D), (FEAT_D,), (FEAT_D,), (FEAT_D, FEAT_D), (FEAT_D,))
+
+
+def feat_check(episodes, n_way, n_support, n_query, D=FEAT_D):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != FEAT_D:
+        raise ValueError("FEAT head: feature dimension %d is not supported (D = %d)" % (D, FEAT_D))
+    if not 1 <= int(n_way) <= FEAT_MAX_WAY:
+        raise ValueError("FEAT head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), FEAT_MAX_WAY))
+    if int(n_support) < 1 or int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("FEAT head: n_support = %d, n_query = %d, episodes = %d (all must be >= 1)"
+                         % (int(n_support), int(n_query), int(episodes)))
+    T = int(n_support) + int(n_query)
+    if T > FEAT_MAX_T:
+        raise ValueError("FEAT head: T = n_support + n_query = %d tokens per class is not supported (T <= %d: one wave holds a "
+                         "softmax row)" % (T, FEAT_MAX_T))
+    rows = int(episodes) * int(n_way) * (T + 1)
+    if rows * FEAT_D >= 2 ** 31 or int(episodes) * int(n_way) * (int(n_way) + T * T) >= 2 ** 31:
+        raise ValueError("FEAT head: episodes * n_way * (T + 1) = %d token rows is not supported (32-bit element counts)" % rows)
+
+
+def feat_counts(episodes, n_way, n_support, n_query, train):
+    """(Ntok, number of [t, t] block elements) of a step: the prototype sets, then -- in train mode -- the class sets."""
+    T, NP = n_support + n_query, episodes * n_way
+    return NP + (NP * T if train else 0), NP * n_way + (NP * T * T if train else 0)
+
+
+def _feat_head(head):
+    head = tuple(head)
+    if len(head) != 7:
+        raise RuntimeError("FEAT head: expected the seven tensors w_qs, w_ks, w_vs, layer_norm.weight, layer_norm.bias, fc.weight, fc.bias")
+    for t, shape in zip(head, FEAT_HEAD_SHAPES):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("FEAT head: the slf_attn tensors must be float32 tensors on the GPU (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError("FEAT head: expected contiguous float32 %s, got %s %s" % (shape, t.dtype, tuple(t.shape)))
+    return head
+
+
+def feat_draw(episodes, n_way, n_support, n_query, seed, index, p_att=FEAT_P_ATT, p_out=FEAT_P_OUT, masks_in=None):
+    """The two dropout multipliers of a train-mode step in one launch: (m_att [blocks], m_out [Ntok, 512]), each 0 or 1 / (1 - p),
+    from Philox4x32-10 keyed by ``seed`` at the draw index read from ``index`` (int64 [1] on the device; the launch stores
+    index + 1, so a replayed hipGraph draws fresh masks).  ``masks_in`` = (m_att, m_out) replaces the draw (tests, golden parity)."""
+    feat_check(episodes, n_way, n_support, n_query)
+    if not index.is_cuda or index.dtype != torch.int64 or index.numel() != 1:
+        raise RuntimeError("FEAT head: the draw index must be an int64 tensor of one element on the GPU")
+    ntok, nblk = feat_counts(episodes, n_way, n_support, n_query, True)
+    m_att = torch.empty(nblk, device=index.device, dtype=torch.float32)
+    m_out = torch.empty((ntok, FEAT_D), device=index.device, dtype=torch.float32)
+    ia = io = None
+    if masks_in is not None:
+        ia, io = masks_in
+        for t, n in ((ia, nblk), (io, ntok * FEAT_D)):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+                raise ValueError("FEAT head: forced masks must be contiguous float32 tensors on the GPU with %d and %d elements"
+                                 % (nblk, ntok * FEAT_D))
+    _lib.call("mft_feat_draw", episodes, n_way, n_support, n_query, FEAT_D, float(p_att), float(p_out), int(seed) & 0xFFFFFFFFFFFFFFFF,
+              _p(index), _p(ia), _p(io), _p(m_att), _p(m_out), _stream())
+    return m_att, m_out
+
+
+def feat_forward(feats, head, episodes, n_way, n_support, n_query, train, masks=None, save=False,
+                 temperature=FEAT_TEMPERATURE, temperature2=FEAT_TEMPERATURE2):
+    """FEAT head forward: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode after
+    the other, row stride >= 512), head = the seven slf_attn tensors in state-dict order -> (scores [episodes*n_way*n_query, n_way],
+    reg [episodes*n_way*(n_support+n_query), n_way] | None, tape | None).  ``train``: also the auxiliary sets (one per class) and
+    their scores ``reg``.  ``masks`` = (m_att, m_out) multipliers (train mode only; None: all 1).  Six launches whatever the shape:
+    tokens, project, attention, fc, norm, scores.  ``save``: keep what feat_backward needs."""
+    if not feats.is_cuda:
+        raise RuntimeError("FEAT head: input is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % feats.device)
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("FEAT head: expected float32 rows [R, D] with unit column stride, got %s %s" % (feats.dtype, tuple(feats.shape)))
+    feat_check(episodes, n_way, n_support, n_query, feats.shape[1])
+    E, D, T, train = episodes, FEAT_D, n_support + n_query, bool(train)
+    rows, Q = E * n_way * T, n_way * n_query
+    if feats.shape[0] != rows:
+        raise ValueError("FEAT head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]" % (tuple(feats.shape), rows, D))
+    if feats.stride(0) < D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("FEAT head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), D))
+    wq, wk, wv, ln_w, ln_b, wfc, bfc = head = _feat_head(head)
+    ntok, nblk = feat_counts(E, n_way, n_support, n_query, train)
+    m_att = m_out = None
+    if masks is not None:
+        if not train:
+            raise ValueError("FEAT head: dropout multipliers exist in train mode only")
+        m_att, m_out = masks
+        for t, n in ((m_att, nblk), (m_out, ntok * D)):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+                raise ValueError("FEAT head: the multipliers must be contiguous float32 tensors on the GPU with %d and %d elements"
+                                 % (nblk, ntok * D))
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    X, qkv, P, o, y, A = new(ntok, D), new(3, ntok, D), new(nblk), new(ntok, D), new(ntok, D), new(ntok, D)
+    mean, rstd, scores = new(ntok), new(ntok), new(E * Q, n_way)
+    centre, reg = (new(E * n_way, D), new(rows, n_way)) if train else (None, None)
+    sh = (E, n_way, n_support, n_query, D, 1 if train else 0)
+    _lib.call("mft_feat_tokens", _p(feats), feats.stride(0), *sh, _p(X), _stream())
+    _lib.call("mft_feat_project", _p(X), *sh, _p(wq), _p(wk), _p(wv), _p(qkv), _stream())
+    _lib.call("mft_feat_attention", _p(qkv), *sh, _p(m_att), _p(P), _p(o), _stream())
+    _lib.call("mft_feat_fc", _p(o), *sh, _p(wfc), _p(bfc), _p(y), _stream())
+    _lib.call("mft_feat_norm", _p(y), _p(X), *sh, _p(m_out), _p(ln_w), _p(ln_b), _p(A), _p(mean), _p(rstd), _stream())
+    _lib.call("mft_feat_scores", _p(feats), feats.stride(0), *sh, _p(A), float(temperature), float(temperature2), _p(scores), _p(centre),
+              _p(reg), _stream())
+    if not save:
+        return scores, reg, None
+    return scores, reg, dict(feats=feats, head=head, X=X, qkv=qkv, P=P, o=o, y=y, A=A, mean=mean, rstd=rstd, centre=centre, m_att=m_att,
+                             m_out=m_out, temps=(float(temperature), float(temperature2)), shape=(E, n_way, n_support, n_query), train=train)
+
+
+def feat_backward(tape, dscores, dreg=None):
+    """d(scores) [episodes*n_way*n_query, n_way] and -- for a train-mode tape -- d(reg) [rows, n_way] (None: zero) -> (dfeats
+    [rows, 512] with every row written once, then the gradients of the seven head tensors in state-dict order).  Six launches
+    whatever the shape: scores, norm, fc, attention, project backward and the dfeats assembly."""
+    E, n_way, n_support, n_query = tape["shape"]
+    train, feats = tape["train"], tape["feats"]
+    wq, wk, wv, ln_w, ln_b, wfc, bfc = tape["head"]
+    D, T, Q = FEAT_D, n_support + n_query, n_way * n_query
+    rows = E * n_way * T
+    for d, shape, name in ((dscores, (E * Q, n_way), "dscores"), (dreg, (rows, n_way), "dreg")):
+        if d is None:
+            continue
+        if not d.is_cuda:
+            raise RuntimeError("FEAT head: %s is on %s -- the MI355X path has no CPU fallback" % (name, d.device))
+        if d.dtype != torch.float32 or not d.is_contiguous() or tuple(d.shape) != shape:
+            raise ValueError("feat_backward: %s must be contiguous float32 %s, got %s %s" % (name, shape, d.dtype, tuple(d.shape)))
+    dev = feats.device
+    if train and dreg is None:
+        dreg = torch.zeros((rows, n_way), device=dev, dtype=torch.float32)
+    if not train and dreg is not None:
+        raise ValueError("feat_backward: d(reg) for an eval-mode tape")
+    ntok, nblk = feat_counts(E, n_way, n_support, n_query, train)
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    ddirect, dA, dy, dXres, d_o, dS, dqkv, dX = new(rows, D), new(ntok, D), new(ntok, D), new(ntok, D), new(ntok, D), new(nblk), new(3, ntok, D), new(ntok, D)
+    dfeats, dW, dln_w, dln_b, dwfc, dbfc = new(rows, D), new(3, D, D), new(D), new(D), new(D, D), new(D)
+    sh = (E, n_way, n_support, n_query, D, 1 if train else 0)
+    t1, t2 = tape["temps"]
+    _lib.call("mft_feat_scores_backward", _p(feats), feats.stride(0), *sh, _p(tape["A"]), _p(tape["centre"]), _p(dscores), _p(dreg), t1, t2,
+              _p(ddirect), _p(dA), _stream())
+    _lib.call("mft_feat_norm_backward", _p(dA), _p(tape["y"]), _p(tape["X"]), *sh, _p(tape["m_out"]), _p(ln_w), _p(tape["mean"]),
+              _p(tape["rstd"]), _p(dy), _p(dXres), _p(dln_w), _p(dln_b), _p(dbfc), _stream())
+    _lib.call("mft_feat_fc_backward", _p(dy), _p(tape["o"]), *sh, _p(wfc), _p(d_o), _p(dwfc), _stream())
+    _lib.call("mft_feat_attention_backward", _p(d_o), _p(tape["qkv"]), _p(tape["P"]), _p(tape["m_att"]), *sh, _p(dS), _p(dqkv), _stream())
+    _lib.call("mft_feat_project_backward", _p(dqkv), _p(tape["X"]), _p(dXres), *sh, _p(wq), _p(wk), _p(wv), _p(dX), _p(dW), _stream())
+    _lib.call("mft_feat_dfeats", _p(ddirect), _p(dX), *sh, _p(dfeats), D, _stream())
+    return dfeats, dW[0], dW[1], dW[2], dln_w, dln_b, dwfc, dbfc
+
+
+def feat_loss(scores, reg, episodes, n_way, n_support, n_query, balance=FEAT_BALANCE, loss_sum=None):
+    """out [3] = (CE(scores) + balance CE(reg), CE(scores), CE(reg)), means, the label of a row being its class, in one launch;
+    ``reg`` None: the main term alone.  ``loss_sum`` (float64 device scalar) += the main term."""
+    out = torch.empty(3, device=scores.device, dtype=torch.float32)
+    _lib.call("mft_feat_loss", _p(scores), _p(reg), episodes, n_way, n_support, n_query, float(balance), _p(out), _p(loss_sum), _stream())
+    return out
+
+
+def feat_loss_backward(scores, reg, episodes, n_way, n_support, n_query, grad_loss, balance=FEAT_BALANCE):
+    """(dscores, dreg | None) of out[0] * grad_loss (a float32 device scalar, None = 1), one launch."""
+    dscores = torch.empty_like(scores)
+    dreg = torch.empty_like(reg) if reg is not None else None
+    _lib.call("mft_feat_loss_backward", _p(scores), _p(reg), episodes, n_way, n_support, n_query, float(balance), _p(grad_loss),
+              _p(dscores), _p(dreg), _stream())
+    return dscores, dreg
+
+
 # ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
 SVM_C = 0.1                        # the published C_reg; a constant of the kernels
 SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1

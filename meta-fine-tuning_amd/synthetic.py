@@ -172,6 +172,39 @@ def tpn_head_state(seed=30, dim=512):
     return sd
 
 
+FEAT_HEAD_KEYS = ("slf_attn.w_qs.weight", "slf_attn.w_ks.weight", "slf_attn.w_vs.weight", "slf_attn.layer_norm.weight",
+                  "slf_attn.layer_norm.bias", "slf_attn.fc.weight", "slf_attn.fc.bias")
+
+
+def feat_head_state(seed=31, dim=512):
+    """The seven FEAT head tensors, state-dict keys and order of methods.feat.FEAT after ``feature.*``, with
+    the constructor's distributions: the three projections ~ N(0, 2 / (dim + dim)), ``layer_norm`` ones and zeros, ``fc.weight``
+    ~ N(0, 2 / (dim + dim)) (xavier_normal_) and ``fc.bias`` ~ U(-1 / sqrt(dim), 1 / sqrt(dim))."""
+    rs = np.random.RandomState(seed)
+    f32 = lambda a: torch.from_numpy(a.astype(np.float32))  # noqa: E731
+    std = np.sqrt(2.0 / (dim + dim))
+    sd = OrderedDict()
+    for k in FEAT_HEAD_KEYS[:3]:
+        sd[k] = f32(std * rs.standard_normal((dim, dim)))
+    sd[FEAT_HEAD_KEYS[3]] = torch.ones(dim, dtype=torch.float32)
+    sd[FEAT_HEAD_KEYS[4]] = torch.zeros(dim, dtype=torch.float32)
+    sd[FEAT_HEAD_KEYS[5]] = f32(std * rs.standard_normal((dim, dim)))
+    sd[FEAT_HEAD_KEYS[6]] = f32(rs.uniform(-1.0, 1.0, dim) / np.sqrt(dim))
+    return sd
+
+
+def feat_masks(seed, episodes, n_way, n_support, n_query, p_att=0.1, p_out=0.5, dim=512):
+    """Forced dropout multipliers of one train-mode FEAT step (tests and golden parity), regenerated from ``seed``: (m_att, m_out)
+    float32 in the layout of ops.feat_draw -- the episodes' [n_way, n_way] blocks, then the classes' [T, T] blocks, flattened;
+    m_out [episodes * n_way * (1 + T), dim] -- each entry 0 with probability p, else 1 / (1 - p) as float32 rounds it."""
+    rs = np.random.RandomState(seed)
+    T, NP = n_support + n_query, episodes * n_way
+    keep = lambda n, p: np.where(rs.random_sample(n) >= p, np.float32(1.0 / (1.0 - float(np.float32(p)))), np.float32(0.0)).astype(np.float32)  # noqa: E731
+    m_att = keep(NP * n_way + NP * T * T, p_att)
+    m_out = keep((NP + NP * T) * dim, p_out).reshape(NP + NP * T, dim)
+    return torch.from_numpy(m_att), torch.from_numpy(m_out)
+
+
 def _templates(rs, n_way, size):
     """Per-class low-frequency templates: 7x7 gaussian grids upsampled bilinearly."""
     low = torch.from_numpy(rs.standard_normal((n_way, 3, 7, 7)).astype(np.float32))
