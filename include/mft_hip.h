@@ -659,6 +659,50 @@ int mft_feat_dfeats(const float* ddirect, const float* dX, int episodes, int n_w
 int mft_feat_draw(int episodes, int n_way, int n_support, int n_query, int D, float p_att, float p_out, unsigned long long seed,
                   unsigned long long* index, const float* in_att, const float* in_out, float* m_att, float* m_out, void* stream);
 
+/* Deep Kernel Transfer head (csrc/dkt.hip): a Gaussian process on the features, every episode of a step per
+ * launch.  feats as for the ridge head (D = 512), N = n_way * (n_support + n_query) rows and S = n_way * n_support support rows per
+ * episode.  The three hyperparameters (mean, raw_outputscale, raw_noise: one float each) and grad_loss are read from DEVICE memory:
+ * s = softplus(raw_outputscale), noise = 1e-4 + softplus(raw_noise).  U [rows, D] and nrm [rows] (float64) are in the row order of
+ * feats.  The POINTS of a launch, M per episode, are every row of the episode in row order (support_only = 0: the loss, M = N) or
+ * the support rows class-major (support_only != 0: the scores, M = S).  K [episodes, M, M] (lower triangle), L [episodes,
+ * M (M + 1) / 2] (packed lower triangle, row after row), A [episodes, M, n_way], V [episodes, N, D], B and W [episodes, n_way, D].
+ *   normalise: nrm = |z|, u = z / max(nrm, 1e-12), or u = z / sqrt(D) with linear != 0.
+ *   gram:      K = s U_P U_P^T + noise I over the points.
+ *   factor:    one workgroup per episode: L = chol(K), A = K^-1 (Y - mean), Y = +1 on the point's class and -1 elsewhere.
+ *              support_only = 0: stats [episodes, 4] (float64) = the episode's loss (tr(R^T A) / 2 + n_way log det K / 2 +
+ *              n_way M log(2 pi) / 2) / M, sum A, sum A^2, log det K; then a one-thread launch behind it stores loss[0] = the mean
+ *              of the episodes' losses (added in episode order) and adds it to *loss_sum (float64, nullable); W must be NULL.
+ *              support_only != 0: W = s U_S^T A; stats and loss must be NULL.  L is nullable (not saved).
+ *   solve:     V = K^-1 U (512 right-hand sides against the saved factor, 32 per workgroup) and B = A^T U, for the loss's points;
+ *              trace [episodes, 16] (float64) = the workgroups' shares of tr K^-1 = |L^-1|_F^2 (the unit vectors, 32 per workgroup).
+ *   backward:  with G = (n_way K^-1 - A A^T) / (2 M): (G U)_i = (n_way V_i - A_i B) / (2 M), dU = 2 s g (G U), g = grad_loss[0] /
+ *              episodes (NULL = 1), then through the normalisation to EVERY row of dfeats (row stride ldd >= D); part [rows]
+ *              (float64) = <(G U)_i, u_i>.
+ *   hyper_backward: (dmean, draw_outputscale, draw_noise: one float each) = g (-sum A / M, sigmoid(raw_outputscale) sum_i part_i,
+ *              sigmoid(raw_noise) tr G) summed over the episodes in order, tr G = (n_way tr K^-1 - sum A^2) / (2 M), tr K^-1 = sum_b trace_b.
+ *   scores:    scores [episodes * n_way * n_query, n_way] = mean + U_Q W, query rows class-major.
+ * Storage fp32, sums in double inside the kernels, fixed summation order, no atomics, no data-dependent trip count.
+ * MFT_EINVAL outside n_way 1..32, M 1..256, n_support / n_query / episodes >= 1, D = 512, ld >= D a multiple of 4 (ldd >= D),
+ * 16-byte aligned feats / U / W, or a factor call whose outputs do not match its support_only. */
+int mft_dkt_normalise(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int linear, float* U,
+                      double* nrm, void* stream);
+int mft_dkt_gram(int episodes, int n_way, int n_support, int n_query, int D, int support_only, const float* U,
+                 const float* raw_outputscale, const float* raw_noise, float* K, void* stream);
+int mft_dkt_factor(int episodes, int n_way, int n_support, int n_query, int D, int support_only, const float* U, const float* K,
+                   const float* mean, const float* raw_outputscale, float* L, float* A, double* stats, float* loss, double* loss_sum,
+                   float* W, void* stream);
+int mft_dkt_solve(int episodes, int n_way, int n_support, int n_query, int D, const float* U, const float* L, const float* A, float* V,
+                  float* B, double* trace, void* stream);
+int mft_dkt_backward(int episodes, int n_way, int n_support, int n_query, int D, int linear, const float* U, const double* nrm,
+                     const float* A, const float* V, const float* B, const float* raw_outputscale, const float* grad_loss,
+                     float* dfeats, int ldd, double* part, void* stream);
+int mft_dkt_hyper_backward(int episodes, int n_way, int n_support, int n_query, int D, const double* part, const double* trace,
+                           const double* stats,
+                           const float* raw_outputscale, const float* raw_noise, const float* grad_loss, float* dmean,
+                           float* draw_outputscale, float* draw_noise, void* stream);
+int mft_dkt_scores(int episodes, int n_way, int n_support, int n_query, int D, const float* U, const float* W, const float* mean,
+                   float* scores, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

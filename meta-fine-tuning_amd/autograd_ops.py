@@ -748,6 +748,63 @@ def feat_loss(scores, reg, episodes, n_way, n_support, n_query, balance=ops.FEAT
     return _FeatLossFn.apply(scores, reg, (episodes, n_way, n_support, n_query), float(balance), loss_sum)
 
 
+class _DktLossFn(torch.autograd.Function):
+    """DKT's negative marginal log-likelihood with a hand-written backward: ops.dkt_loss_forward keeps the
+    normalised rows, the packed Cholesky factor, A = K^-1 R and the per-episode sums; ops.dkt_loss_backward returns the gradients of
+    every feature row and of the three hyperparameters, with the upstream gradient read on the device."""
+
+    @staticmethod
+    def forward(ctx, feats, mean, raw_outputscale, raw_noise, shape, kernel, loss_sum):
+        hyper = tuple(p.detach() for p in (mean, raw_outputscale, raw_noise))
+        loss, tape = ops.dkt_loss_forward(feats, hyper, *shape, kernel=kernel, save=True, loss_sum=loss_sum)
+        ctx.tape = {k: v for k, v in tape.items() if k != "feats"}       # (the backward reads U and |z|, not the rows themselves)
+        ctx.shapes = tuple(p.shape for p in (mean, raw_outputscale, raw_noise))
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if g.dtype != torch.float32 or g.numel() != 1:
+            g = g.reshape(-1)[:1].float()
+        dfeats, dhyper = ops.dkt_loss_backward(ctx.tape, g)
+        need = ctx.needs_input_grad
+        return (dfeats if need[0] else None,) + tuple(dhyper[i].view(ctx.shapes[i]) if need[1 + i] else None for i in range(3)) \
+            + (None, None, None)
+
+
+def _dkt_inputs(what, feats, hyper, episodes, n_way, n_support, n_query, loss):
+    _require_cuda(feats, what)
+    for p in hyper:
+        _require_cuda(p, what)
+    ops.dkt_check(episodes, n_way, n_support, n_query, feats.shape[-1], loss)
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    return feats
+
+
+def dkt_loss(feats, mean, raw_outputscale, raw_noise, n_way, n_support, n_query, episodes=1, kernel="cossim", loss_sum=None):
+    """DKT.set_forward_loss tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one
+    episode after the other) and the three one-element hyperparameters -> the 0-dim loss: the negative marginal log-likelihood of
+    the n_way one-vs-rest Gaussian processes over ALL rows of the episode, divided by their number, averaged over the episodes.
+    Differentiable (features and the three hyperparameters) when autograd records; the no-grad path saves nothing.  ``loss_sum``
+    (float64 device scalar) += the loss."""
+    hyper = (mean, raw_outputscale, raw_noise)
+    feats = _dkt_inputs("DKT loss", feats, hyper, episodes, n_way, n_support, n_query, True)
+    ops.dkt_kernel_id(kernel)
+    if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in hyper)):
+        return _DktLossFn.apply(feats, *hyper, (episodes, n_way, n_support, n_query), kernel, loss_sum)
+    return ops.dkt_loss_forward(feats.detach(), tuple(p.detach() for p in hyper), episodes, n_way, n_support, n_query, kernel=kernel,
+                                loss_sum=loss_sum)[0].view(())
+
+
+def dkt_scores(feats, mean, raw_outputscale, raw_noise, n_way, n_support, n_query, episodes=1, kernel="cossim"):
+    """DKT.set_forward tail: the posterior mean of the process conditioned on each episode's support rows, at its queries ->
+    scores [episodes*n_way*n_query, n_way].  A prediction: the returned tensor never requires grad (the method trains through
+    ``dkt_loss`` and never differentiates through its scores)."""
+    hyper = (mean, raw_outputscale, raw_noise)
+    feats = _dkt_inputs("DKT head", feats, hyper, episodes, n_way, n_support, n_query, False)
+    return ops.dkt_scores(feats.detach(), tuple(p.detach() for p in hyper), episodes, n_way, n_support, n_query, kernel=kernel)
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

@@ -60,47 +60,6 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_gram_kernel(const float* 
         }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- solves
-// L (packed lower triangle in LDS) against n_way right-hand sides.  Thread (c = tid / 32, part = tid % 32) keeps the rows
-// j = part (mod 32) of column c in registers (slot j / 32): row k's value is reduced over the 32 lanes of the group and kept by
-// lane k % 32.  No workgroup barrier: L is only read.  On entry v[] holds the right-hand side, on exit the solution.
-__device__ __forceinline__ void solve_lower(const float* __restrict__ sl, int S, int part, double (&v)[8]) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        for (int kk = 0; kk < 32; ++kk) {
-            const int k = 32 * t + kk;
-            if (k >= S) break;                                   // uniform over the workgroup
-            const int rowk = k * (k + 1) / 2;
-            double acc = part == kk ? v[t] : 0.0;
-#pragma unroll
-            for (int tt = 0; tt <= t; ++tt) {
-                const int j = 32 * tt + part;
-                if (j < k) acc -= (double)sl[rowk + j] * v[tt];
-            }
-            acc = group_sum<32>(acc);
-            if (part == kk) v[t] = acc / (double)sl[rowk + k];
-        }
-    }
-}
-
-__device__ __forceinline__ void solve_lower_transposed(const float* __restrict__ sl, int S, int part, double (&v)[8]) {
-#pragma unroll
-    for (int t = 7; t >= 0; --t) {
-        for (int kk = 31; kk >= 0; --kk) {
-            const int k = 32 * t + kk;
-            if (k >= S) continue;                                // uniform over the workgroup
-            double acc = part == kk ? v[t] : 0.0;
-#pragma unroll
-            for (int tt = t; tt < 8; ++tt) {
-                const int j = 32 * tt + part;
-                if (j > k && j < S) acc -= (double)sl[j * (j + 1) / 2 + k] * v[tt];
-            }
-            acc = group_sum<32>(acc);
-            if (part == kk) v[t] = acc / (double)sl[k * (k + 1) / 2 + k];
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- factor
 // one workgroup per episode: Cholesky factor of A in LDS (left-looking, four threads per row), L back to the workspace,
 // alpha = 2 L^-T L^-1 Y, W = Z_S^T alpha

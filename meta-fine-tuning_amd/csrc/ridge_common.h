@@ -1,5 +1,6 @@
 // Episode layout, domain and small device helpers shared by the two MetaOptNet heads: csrc/ridge.hip and
-// csrc/svm.hip (section 17).
+// csrc/svm.hip (section 17); the packed-triangle Cholesky factor and the two triangular solves also serve csrc/tpn.hip (section 18)
+// and csrc/dkt.hip (section 20).
 #pragma once
 #include "mft_common.h"
 
@@ -89,6 +90,67 @@ __device__ __forceinline__ void support_assemble(const float* __restrict__ ep, c
                 dep[(long long)(cl * (s.ns + s.nq) + (i - cl * s.ns)) * ldd + d] = (float)acc[q];
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- solves
+// L (packed lower triangle in LDS) against up to 32 right-hand sides.  Thread (c = tid / 32, part = tid % 32) keeps the rows
+// j = part (mod 32) of column c in registers (slot j / 32): row k's value is reduced over the 32 lanes of the group and kept by
+// lane k % 32.  No workgroup barrier: L is only read.  On entry v[] holds the right-hand side, on exit the solution.
+__device__ __forceinline__ void solve_lower(const float* __restrict__ sl, int S, int part, double (&v)[8]) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        for (int kk = 0; kk < 32; ++kk) {
+            const int k = 32 * t + kk;
+            if (k >= S) break;                                   // uniform over the workgroup
+            const int rowk = k * (k + 1) / 2;
+            double acc = part == kk ? v[t] : 0.0;
+#pragma unroll
+            for (int tt = 0; tt <= t; ++tt) {
+                const int j = 32 * tt + part;
+                if (j < k) acc -= (double)sl[rowk + j] * v[tt];
+            }
+            acc = group_sum<32>(acc);
+            if (part == kk) v[t] = acc / (double)sl[rowk + k];
+        }
+    }
+}
+
+__device__ __forceinline__ void solve_lower_transposed(const float* __restrict__ sl, int S, int part, double (&v)[8]) {
+#pragma unroll
+    for (int t = 7; t >= 0; --t) {
+        for (int kk = 31; kk >= 0; --kk) {
+            const int k = 32 * t + kk;
+            if (k >= S) continue;                                // uniform over the workgroup
+            double acc = part == kk ? v[t] : 0.0;
+#pragma unroll
+            for (int tt = t; tt < 8; ++tt) {
+                const int j = 32 * tt + part;
+                if (j > k && j < S) acc -= (double)sl[j * (j + 1) / 2 + k] * v[tt];
+            }
+            acc = group_sum<32>(acc);
+            if (part == kk) v[t] = acc / (double)sl[k * (k + 1) / 2 + k];
+        }
+    }
+}
+
+// left-looking Cholesky of the packed lower triangle in LDS, in place, by the whole workgroup: PARTS threads per row share the
+// row's dot product with column kc; the diagonal entry is rounded to fp32 before the column is divided by it
+template <int PARTS>
+__device__ __forceinline__ void cholesky_packed(float* __restrict__ sl, int N, int tid, double* __restrict__ sdiag) {
+    const int i = tid / PARTS, part = tid % PARTS, rowi = i * (i + 1) / 2;
+    for (int kc = 0; kc < N; ++kc) {
+        const int rowk = kc * (kc + 1) / 2;
+        const bool live = i >= kc && i < N;
+        double acc = 0.0;
+        if (live)
+            for (int j = part; j < kc; j += PARTS) acc += (double)sl[rowi + j] * (double)sl[rowk + j];
+        acc = group_sum<PARTS>(acc);
+        const double v = live ? (double)sl[rowi + kc] - acc : 0.0;
+        if (i == kc && part == 0) *sdiag = (double)(float)sqrt(v);
+        __syncthreads();
+        if (live && part == 0) sl[rowi + kc] = i == kc ? (float)*sdiag : (float)(v / *sdiag);
+        __syncthreads();
     }
 }
 

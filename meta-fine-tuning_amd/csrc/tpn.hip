@@ -126,66 +126,6 @@ __global__ __launch_bounds__(RIDGE_THREADS) void tpn_affinity_kernel(const float
         }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- solves
-// the two triangular solves of csrc/ridge.hip on N nodes: L (packed lower triangle in LDS) against n_way right-hand sides; thread
-// (c = tid / 32, part = tid % 32) keeps the rows j = part (mod 32) of column c in registers (slot j / 32)
-__device__ __forceinline__ void tpn_solve_lower(const float* __restrict__ sl, int N, int part, double (&v)[8]) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        for (int kk = 0; kk < 32; ++kk) {
-            const int k = 32 * t + kk;
-            if (k >= N) break;                                   // uniform over the workgroup
-            const int rowk = k * (k + 1) / 2;
-            double acc = part == kk ? v[t] : 0.0;
-#pragma unroll
-            for (int tt = 0; tt <= t; ++tt) {
-                const int j = 32 * tt + part;
-                if (j < k) acc -= (double)sl[rowk + j] * v[tt];
-            }
-            acc = group_sum<32>(acc);
-            if (part == kk) v[t] = acc / (double)sl[rowk + k];
-        }
-    }
-}
-
-__device__ __forceinline__ void tpn_solve_lower_transposed(const float* __restrict__ sl, int N, int part, double (&v)[8]) {
-#pragma unroll
-    for (int t = 7; t >= 0; --t) {
-        for (int kk = 31; kk >= 0; --kk) {
-            const int k = 32 * t + kk;
-            if (k >= N) continue;                                // uniform over the workgroup
-            double acc = part == kk ? v[t] : 0.0;
-#pragma unroll
-            for (int tt = t; tt < 8; ++tt) {
-                const int j = 32 * tt + part;
-                if (j > k && j < N) acc -= (double)sl[j * (j + 1) / 2 + k] * v[tt];
-            }
-            acc = group_sum<32>(acc);
-            if (part == kk) v[t] = acc / (double)sl[k * (k + 1) / 2 + k];
-        }
-    }
-}
-
-// left-looking Cholesky of the packed lower triangle in LDS, in place, by the whole workgroup: PARTS threads per row share the
-// row's dot product with column kc; the diagonal entry is rounded to fp32 before the column is divided by it
-template <int PARTS>
-__device__ __forceinline__ void tpn_cholesky(float* __restrict__ sl, int N, int tid, double* __restrict__ sdiag) {
-    const int i = tid / PARTS, part = tid % PARTS, rowi = i * (i + 1) / 2;
-    for (int kc = 0; kc < N; ++kc) {
-        const int rowk = kc * (kc + 1) / 2;
-        const bool live = i >= kc && i < N;
-        double acc = 0.0;
-        if (live)
-            for (int j = part; j < kc; j += PARTS) acc += (double)sl[rowi + j] * (double)sl[rowk + j];
-        acc = group_sum<PARTS>(acc);
-        const double v = live ? (double)sl[rowi + kc] - acc : 0.0;
-        if (i == kc && part == 0) *sdiag = (double)(float)sqrt(v);
-        __syncthreads();
-        if (live && part == 0) sl[rowi + kc] = i == kc ? (float)*sdiag : (float)(v / *sdiag);
-        __syncthreads();
-    }
-}
-
 __device__ __forceinline__ bool sel_bit(const unsigned int* __restrict__ bits, int i, int j) {
     return (bits[i * (TPN_MAX_N / 32) + (j >> 5)] >> (j & 31)) & 1u;
 }
@@ -269,9 +209,9 @@ __global__ __launch_bounds__(RIDGE_WG) void tpn_propagate_kernel(const float* __
     }
     __syncthreads();
     // 1024 threads over N rows: 4 threads per row up to 256 rows, 8 up to 128, 16 up to 64 (a function of the shape alone)
-    if (N > 128) tpn_cholesky<4>(sl, N, tid, &sdiag);
-    else if (N > 64) tpn_cholesky<8>(sl, N, tid, &sdiag);
-    else tpn_cholesky<16>(sl, N, tid, &sdiag);
+    if (N > 128) cholesky_packed<4>(sl, N, tid, &sdiag);
+    else if (N > 64) cholesky_packed<8>(sl, N, tid, &sdiag);
+    else cholesky_packed<16>(sl, N, tid, &sdiag);
     const int packed = N * (N + 1) / 2;
     if (L) {
         float* Le = L + (long long)e * packed;
@@ -284,8 +224,8 @@ __global__ __launch_bounds__(RIDGE_WG) void tpn_propagate_kernel(const float* __
         const int j = 32 * t + part;
         v[t] = (j < S && j / s.ns == c) ? 1.0 : 0.0;
     }
-    tpn_solve_lower(sl, N, part, v);
-    tpn_solve_lower_transposed(sl, N, part, v);
+    solve_lower(sl, N, part, v);
+    solve_lower_transposed(sl, N, part, v);
     const int Q = s.n_way * s.nq;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -327,8 +267,8 @@ __global__ __launch_bounds__(RIDGE_WG) void tpn_propagate_bwd_kernel(const float
         v[t] = (j >= S && j < N && c < nw) ? (double)dscores[((long long)e * Q + (j - S)) * ldg + c] : 0.0;
     }
     __syncthreads();
-    tpn_solve_lower(sl, N, part, v);
-    tpn_solve_lower_transposed(sl, N, part, v);
+    solve_lower(sl, N, part, v);
+    solve_lower_transposed(sl, N, part, v);
     __syncthreads();                                             // L is dead: Lambda and F [N][n_way] follow
     float* slam = sl;
     float* sf = sl + N * nw;

@@ -11,15 +11,23 @@ from . import backbone
 model_dict = dict(ResNet10=backbone.ResNet10, ResNet10_FW=backbone.ResNet10_FW)      # ResNet18 is off the hot path; ResNet10_FW: DESIGN §15
 
 HEADS = ("ridge", "svm")             # MetaOptNet's heads (DESIGN.md sections 14 and 17)
+KERNELS = ("cossim", "linear")       # DKT's kernels
 
 
-def method_dir_name(method, head="ridge"):
-    """The method's part of a checkpoint / feature directory name: ``metaoptnet_svm`` for the SVM head, the method otherwise (the
-    default head changes no name)."""
+def method_dir_name(method, head="ridge", kernel=None):
+    """The method's part of a checkpoint / feature directory name: ``metaoptnet_svm`` for the SVM head, ``dkt_linear`` for DKT's
+    linear kernel, the method otherwise (the default head and the default kernel change no name)."""
+    kernel = KERNELS[0] if kernel is None else kernel
     if head not in HEADS:
         raise ValueError("--head %r: %s" % (head, " or ".join(HEADS)))
+    if kernel not in KERNELS:
+        raise ValueError("--kernel %r: %s" % (kernel, " or ".join(KERNELS)))
     if head != "ridge" and method != "metaoptnet":
         raise ValueError("--head %s belongs to --method metaoptnet, not to --method %s" % (head, method))
+    if kernel != KERNELS[0] and method != "dkt":
+        raise ValueError("--kernel %s belongs to --method dkt, not to --method %s" % (kernel, method))
+    if kernel != KERNELS[0]:
+        return "%s_%s" % (method, kernel)
     return method if head == "ridge" else "%s_%s" % (method, head)
 
 
@@ -29,8 +37,9 @@ _COMMON = [
     ("--test_dataset", dict(default="", help="test dataset")),
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
-    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/feat/gnnnet/all")),
+    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/feat/dkt/gnnnet/all")),
     ("--head", dict(default="ridge", help="--method metaoptnet: its head, ridge (ridge regression) or svm")),
+    ("--kernel", dict(default="cossim", help="--method dkt: its kernel, cossim (cosine similarity) or linear")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),
     ("--test_n_way", dict(default=5, type=int, help="class num to classify for testing (validation)")),
     ("--n_shot", dict(default=5, type=int, help="number of labeled data in each class, same as n_support")),

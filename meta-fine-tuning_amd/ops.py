@@ -1601,6 +1601,126 @@ def feat_loss_backward(scores, reg, episodes, n_way, n_support, n_query, grad_lo
     return dscores, dreg
 
 
+# ---------------------------------------------------------------------------------------------- DKT head (csrc/dkt.hip)
+DKT_D, DKT_MAX_M, DKT_MAX_WAY = 512, 256, 32
+DKT_KERNELS = ("cossim", "linear")
+DKT_NOISE_FLOOR, DKT_NOISE_INIT = 1e-4, 0.1        # noise = DKT_NOISE_FLOOR + softplus(raw_noise); the constructor's noise
+DKT_LOSS_LAUNCHES, DKT_BACKWARD_LAUNCHES, DKT_SCORES_LAUNCHES = 3, 3, 4
+
+
+def dkt_check(episodes, n_way, n_support, n_query, D=DKT_D, loss=True):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched.  ``loss``: the
+    marginal likelihood conditions on all N = n_way * (n_support + n_query) rows of the episode; the scores (``loss=False``) on
+    the S = n_way * n_support support rows only, with any n_query."""
+    if D != DKT_D:
+        raise ValueError("DKT head: feature dimension %d is not supported (D = %d)" % (D, DKT_D))
+    if not 1 <= int(n_way) <= DKT_MAX_WAY:
+        raise ValueError("DKT head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), DKT_MAX_WAY))
+    if int(n_support) < 1 or int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("DKT head: n_support = %d, n_query = %d, episodes = %d (all must be >= 1)"
+                         % (int(n_support), int(n_query), int(episodes)))
+    if loss and int(n_way) * (int(n_support) + int(n_query)) > DKT_MAX_M:
+        raise ValueError("DKT loss: N = n_way * (n_support + n_query) = %d rows is not supported (N <= %d: the factor of one episode's "
+                         "kernel matrix is kept in one workgroup's LDS)" % (int(n_way) * (int(n_support) + int(n_query)), DKT_MAX_M))
+    if int(n_way) * int(n_support) > DKT_MAX_M:
+        raise ValueError("DKT head: S = n_way * n_support = %d is not supported (S <= %d)" % (int(n_way) * int(n_support), DKT_MAX_M))
+
+
+def dkt_kernel_id(kernel):
+    if kernel not in DKT_KERNELS:
+        raise ValueError("DKT head: kernel %r (%s)" % (kernel, " or ".join(DKT_KERNELS)))
+    return DKT_KERNELS.index(kernel)
+
+
+def _dkt_args(feats, hyper, episodes, n_way, n_support, n_query, loss):
+    if not feats.is_cuda:
+        raise RuntimeError("DKT head: input is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % feats.device)
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("DKT head: expected float32 rows [R, D] with unit column stride, got %s %s" % (feats.dtype, tuple(feats.shape)))
+    dkt_check(episodes, n_way, n_support, n_query, feats.shape[1], loss)
+    N = n_way * (n_support + n_query)
+    if feats.shape[0] != episodes * N:
+        raise ValueError("DKT head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]" % (tuple(feats.shape), episodes * N, DKT_D))
+    if feats.stride(0) < DKT_D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("DKT head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), DKT_D))
+    if len(hyper) != 3:
+        raise ValueError("DKT head: hyper = (mean, raw_outputscale, raw_noise)")
+    for t in hyper:
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.numel() != 1:
+            raise RuntimeError("DKT head: mean, raw_outputscale and raw_noise must be one-element float32 tensors on the GPU (no CPU fallback)")
+    return tuple(hyper)
+
+
+def dkt_loss_forward(feats, hyper, episodes, n_way, n_support, n_query, kernel="cossim", save=False, loss_sum=None):
+    """DKT training loss: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode after
+    the other, row stride >= 512), hyper = (mean, raw_outputscale, raw_noise) one-element device tensors -> (loss [1] = the mean
+    over the episodes of the negative marginal log-likelihood of the n_way one-vs-rest processes over N, tape | None).  Three
+    launchers whatever the shape: normalise, Gram, factor (which queues the one-thread mean behind it).  ``save``: keep U, the
+    row norms, the packed factor, A and the per-episode sums for dkt_loss_backward.  ``loss_sum`` (float64 device scalar) += loss."""
+    mean, ros, rno = _dkt_args(feats, hyper, episodes, n_way, n_support, n_query, True)
+    lin = dkt_kernel_id(kernel)
+    E, D, N = episodes, DKT_D, n_way * (n_support + n_query)
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    U, K, A, loss = new(E * N, D), new(E, N, N), new(E, N, n_way), new(1)
+    nrm = torch.empty(E * N, device=dev, dtype=torch.float64)
+    stats = torch.empty((E, 4), device=dev, dtype=torch.float64)
+    L = new(E, N * (N + 1) // 2) if save else None
+    _lib.call("mft_dkt_normalise", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, lin, _p(U), _p(nrm), _stream())
+    _lib.call("mft_dkt_gram", E, n_way, n_support, n_query, D, 0, _p(U), _p(ros), _p(rno), _p(K), _stream())
+    _lib.call("mft_dkt_factor", E, n_way, n_support, n_query, D, 0, _p(U), _p(K), _p(mean), _p(ros), _p(L), _p(A), _p(stats), _p(loss),
+              _p(loss_sum), None, _stream())
+    if not save:
+        return loss, None
+    return loss, dict(feats=feats, hyper=(mean, ros, rno), U=U, nrm=nrm, L=L, A=A, stats=stats, linear=lin,
+                      shape=(E, n_way, n_support, n_query))
+
+
+def dkt_loss_backward(tape, grad_loss=None):
+    """(dfeats [rows, 512] with every row written, (dmean, draw_outputscale, draw_noise) [1] each) from the forward's
+    tape, times ``grad_loss`` (a one-element float32 device tensor; None = 1).  Three launches whatever the shape: the 512
+    right-hand sides V = K^-1 U against the saved factor with B = A^T U and tr K^-1, the feature gradient, the three scalar sums."""
+    E, n_way, n_support, n_query = tape["shape"]
+    mean, ros, rno = tape["hyper"]
+    D, N = DKT_D, n_way * (n_support + n_query)
+    dev = tape["U"].device
+    if grad_loss is not None:
+        if not grad_loss.is_cuda:
+            raise RuntimeError("DKT head: d(loss) is on %s -- the MI355X path has no CPU fallback" % grad_loss.device)
+        if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
+            raise RuntimeError("DKT head: expected a one-element float32 d(loss)")
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    V, B, dfeats, dhyper = new(E, N, D), new(E, n_way, D), new(E * N, D), (new(1), new(1), new(1))
+    part = torch.empty(E * N, device=dev, dtype=torch.float64)
+    trace = torch.empty((E, 16), device=dev, dtype=torch.float64)
+    _lib.call("mft_dkt_solve", E, n_way, n_support, n_query, D, _p(tape["U"]), _p(tape["L"]), _p(tape["A"]), _p(V), _p(B), _p(trace),
+              _stream())
+    _lib.call("mft_dkt_backward", E, n_way, n_support, n_query, D, tape["linear"], _p(tape["U"]), _p(tape["nrm"]), _p(tape["A"]), _p(V),
+              _p(B), _p(ros), _p(grad_loss), _p(dfeats), D, _p(part), _stream())
+    _lib.call("mft_dkt_hyper_backward", E, n_way, n_support, n_query, D, _p(part), _p(trace), _p(tape["stats"]), _p(ros), _p(rno), _p(grad_loss),
+              _p(dhyper[0]), _p(dhyper[1]), _p(dhyper[2]), _stream())
+    return dfeats, dhyper
+
+
+def dkt_scores(feats, hyper, episodes, n_way, n_support, n_query, kernel="cossim"):
+    """DKT posterior mean: the process conditioned on the S support rows of each episode, evaluated at its
+    queries -> scores [episodes*n_way*n_query, n_way], row = class * n_query + q.  Four launches whatever the shape: normalise,
+    Gram of the support rows, factor + A_S + W, scores.  A prediction: nothing is saved and nothing is differentiable."""
+    mean, ros, rno = _dkt_args(feats, hyper, episodes, n_way, n_support, n_query, False)
+    lin = dkt_kernel_id(kernel)
+    E, D, N, S, Q = episodes, DKT_D, n_way * (n_support + n_query), n_way * n_support, n_way * n_query
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    U, K, A, W, scores = new(E * N, D), new(E, S, S), new(E, S, n_way), new(E, n_way, D), new(E * Q, n_way)
+    nrm = torch.empty(E * N, device=dev, dtype=torch.float64)
+    _lib.call("mft_dkt_normalise", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, lin, _p(U), _p(nrm), _stream())
+    _lib.call("mft_dkt_gram", E, n_way, n_support, n_query, D, 1, _p(U), _p(ros), _p(rno), _p(K), _stream())
+    _lib.call("mft_dkt_factor", E, n_way, n_support, n_query, D, 1, _p(U), _p(K), _p(mean), _p(ros), None, _p(A), None, None, None, _p(W),
+              _stream())
+    _lib.call("mft_dkt_scores", E, n_way, n_support, n_query, D, _p(U), _p(W), _p(mean), _p(scores), _stream())
+    return scores
+
+
 # ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
 SVM_C = 0.1                        # the published C_reg; a constant of the kernels
 SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1

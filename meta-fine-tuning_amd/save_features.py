@@ -15,7 +15,7 @@ from .data.feature_loader import save_features_file
 from .io_utils import get_assigned_file, get_best_file, get_resume_file, method_dir_name, model_dict, parse_args
 
 BASELINES = ('baseline', 'baseline++')
-METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat')
+METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt')
 SPLIT_SEEDS = {'base': 0, 'val': 2, 'novel': 3}       # miniImageNet-shaped pool per --split; 'base' is train.main's pool (seed 0)
 TEST_DATASET_SEED = 1                                 # --test_dataset X: the pool finetune.main evaluates on
 CHUNK = 200                                           # images per backbone forward
@@ -28,8 +28,9 @@ def check_method(method):
 
 def checkpoint_dir(p):
     """The directory train.main writes: <save_dir>/checkpoints/<dataset>/<model>_<method>[_aug][_<train_n_way>way_<n_shot>shot]
-    (the two baselines carry no way / shot suffix, train.py:176-180; ``--head svm``: <method> reads metaoptnet_svm)."""
-    d = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, p.dataset, p.model, method_dir_name(p.method, getattr(p, "head", "ridge")))
+    (the two baselines carry no way / shot suffix, train.py:176-180; ``--head svm``: <method> reads metaoptnet_svm; ``--kernel linear``: dkt_linear)."""
+    d = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, p.dataset, p.model,
+                                     method_dir_name(p.method, getattr(p, "head", "ridge"), getattr(p, "kernel", None)))
     if p.train_aug:
         d += '_aug'
     if p.method not in BASELINES:
@@ -62,7 +63,7 @@ def resolve_state(p, verbose=True):
         # the stand-in is a GnnNet state: keep its backbone, put the method's own seeded head behind it
         state = type(state)((k, v) for k, v in state.items() if k.startswith("feature."))
         state.update({'matchingnet': synthetic.matchingnet_head_state, 'metaoptnet': synthetic.metaoptnet_head_state,
-                      'tpn': synthetic.tpn_head_state, 'feat': synthetic.feat_head_state}.get(p.method, dict)())
+                      'tpn': synthetic.tpn_head_state, 'feat': synthetic.feat_head_state, 'dkt': synthetic.dkt_head_state}.get(p.method, dict)())
     return state, loaded
 
 

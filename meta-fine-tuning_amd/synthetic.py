@@ -172,6 +172,19 @@ def tpn_head_state(seed=30, dim=512):
     return sd
 
 
+def dkt_head_state(seed=32):
+    """The three DKT hyperparameters, state-dict keys and order of methods.dkt.DKT after ``feature.*``, a
+    little off the constructor's values so that a stand-in run exercises all three: ``gp.mean`` ~ 0.05 N(0,1),
+    ``gp.raw_outputscale`` ~ 0.3 N(0,1), ``gp.raw_noise`` = the constructor's value + 0.3 N(0,1)."""
+    rs = np.random.RandomState(seed)
+    f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32).reshape(1))  # noqa: E731
+    sd = OrderedDict()
+    sd["gp.mean"] = f32(0.05 * rs.standard_normal())
+    sd["gp.raw_outputscale"] = f32(0.3 * rs.standard_normal())
+    sd["gp.raw_noise"] = f32(np.log(np.expm1(0.1 - 1e-4)) + 0.3 * rs.standard_normal())
+    return sd
+
+
 FEAT_HEAD_KEYS = ("slf_attn.w_qs.weight", "slf_attn.w_ks.weight", "slf_attn.w_vs.weight", "slf_attn.layer_norm.weight",
                   "slf_attn.layer_norm.bias", "slf_attn.fc.weight", "slf_attn.fc.bias")
 

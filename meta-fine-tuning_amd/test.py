@@ -20,7 +20,7 @@ def load_model(params):
     """The method's model at --test_n_way / --n_shot on the GPU.  Every method except the two baselines loads its checkpoint (the
     head's weights score the episodes); the baselines train a fresh head per episode.  -> (model, checkpoint file | None)."""
     model = feature_eval.build_model(params.method, model_dict[params.model], params.test_n_way, params.n_shot,
-                                     head=getattr(params, "head", "ridge")).cuda()
+                                     head=getattr(params, "head", "ridge"), kernel=getattr(params, "kernel", None)).cuda()
     loaded = None
     if params.method not in save_features.BASELINES:
         state, loaded = save_features.resolve_state(params)

@@ -1,4 +1,4 @@
-"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / tpn / feat / baseline / baseline++): Adam over all parameters, 100
+"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / tpn / feat / dkt / baseline / baseline++): Adam over all parameters, 100
 episodes per epoch, checkpoints ``{'epoch','state'}`` under <save_dir>/checkpoints/<dataset>/<model>_<method>
 [_aug]_<n>way_<k>shot/<epoch>.tar, optional first-order-MAML meta-fine-tuning (--fine_tune).
 The episode source is the in-repo synthetic miniImageNet-shaped sampler (real data is out of scope)."""
@@ -14,17 +14,19 @@ from .methods.gnnnet import GnnNet
 from .methods.matchingnet import MatchingNet
 from .methods.metaoptnet import MetaOptNet
 from .methods.protonet import ProtoNet
+from .methods.dkt import DKT
 from .methods.feat import FEAT
 from .methods.tpn import TPN
 
 HEAD_METHODS = {'protonet': ProtoNet, 'matchingnet': MatchingNet, 'metaoptnet': MetaOptNet}      # --method -> class (train.py:138-139)
 TRANSDUCTIVE_METHODS = {'tpn': TPN}     # HeadMethods that score an episode's queries together: trained and scored by `test`, no test-time engine mode
 EMBEDDING_METHODS = {'feat': FEAT}      # HeadMethods that adapt the embedding to the episode: trained and scored by `test`, no test-time engine mode
+PROBABILISTIC_METHODS = {'dkt': DKT}    # HeadMethods trained through a marginal likelihood instead of scores: scored by `test`, no test-time engine mode
 
 
 def head_method(name):
-    """The HeadMethod class of ``--method name`` over the three tables, or None."""
-    return HEAD_METHODS.get(name) or TRANSDUCTIVE_METHODS.get(name) or EMBEDDING_METHODS.get(name)
+    """The HeadMethod class of ``--method name`` over the four tables, or None."""
+    return HEAD_METHODS.get(name) or TRANSDUCTIVE_METHODS.get(name) or EMBEDDING_METHODS.get(name) or PROBABILISTIC_METHODS.get(name)
 
 
 class SyntheticEpisodeLoader:
@@ -235,8 +237,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     rank, W = parallel.world()
     if not params.start_epoch > 0:
         np.random.seed(10)
-    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'baseline' and 'baseline++' are on the HIP path"
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'baseline' and 'baseline++' are on the HIP path"
                                   % params.method)
     if head_method(params.method) is not None and params.fine_tune:
         raise NotImplementedError("--method %s --fine_tune: %s's first-order-MAML meta-training is not on the HIP path"
@@ -245,7 +247,7 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
         raise NotImplementedError("--model ResNet10_FW --fine_tune: the reference keeps the feature-wise noise on inside the inner loop, "
                                   "and the fused inner-loop kernels have no per-episode affine; meta-train ResNet10_FW without --fine_tune")
     params.checkpoint_dir = '%s/checkpoints/%s/%s_%s' % (configs.save_dir, params.dataset, params.model,
-                                                         method_dir_name(params.method, params.head))
+                                                         method_dir_name(params.method, params.head, getattr(params, "kernel", None)))
     if params.train_aug:
         params.checkpoint_dir += '_aug'
     if params.method in ('baseline', 'baseline++'):                      # train.py:101-108,176-180
@@ -269,6 +271,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
             cls = gnnnet_copy.GnnNet if (variant50 and params.n_shot == 50) else GnnNet          # train_50.py:154-157
         torch.manual_seed(0) if W > 1 else None
         kw = dict(head=params.head) if params.method == 'metaoptnet' else {}
+        if params.method == 'dkt':
+            kw = dict(kernel=params.kernel)
         model = cls(model_dict[params.model], n_way=params.train_n_way, n_support=params.n_shot, **kw).cuda()
         params.checkpoint_dir += '_%dway_%dshot' % (params.train_n_way, params.n_shot)
     os.makedirs(params.checkpoint_dir, exist_ok=True)
