@@ -703,6 +703,34 @@ int mft_dkt_hyper_backward(int episodes, int n_way, int n_support, int n_query, 
 int mft_dkt_scores(int episodes, int n_way, int n_support, int n_query, int D, const float* U, const float* W, const float* mean,
                    float* scores, void* stream);
 
+/* ANIL head (csrc/anil.hip): K = inner_steps gradient steps of step size a = inner_lr on a linear classifier,
+ * on the support rows of each episode, and the exact second-order backward through them; every episode of a step per launch.  feats as
+ * for the ridge head (D = 512, row stride ld), S = n_way * n_support support rows and Q = n_way * n_query query rows per episode,
+ * Y = the one-hot labels of the class-major rows.  W0 [n_way, D], b0 [n_way].  The tape: Wt [episodes, K + 1, n_way, D] and
+ * bt [episodes, K + 1, n_way] (slot t = the classifier after t steps), P [episodes, K, S, n_way] (slot t = softmax(Z_S W_t^T + b_t));
+ * gWt / gbt have the shapes of Wt / bt (slot t = d loss / d W_t, d b_t of the episode), R [episodes, K, S, n_way].
+ *   adapt:            one workgroup per episode: slot 0 = (W0, b0); for t = 0 .. K-1: P_t, W_{t+1} = W_t - (a / S) (P_t - Y)^T Z_S,
+ *                     b_{t+1} = b_t - (a / S) sum_rows (P_t - Y).  P is nullable (not saved).
+ *   scores:           scores [episodes * Q, n_way] = Z_Q W_K^T + b_K, query rows class-major.
+ *   scores_backward:  with G = dscores (DEVICE memory): the query rows of dfeats (row stride ldd >= D) = G W_K, slot K of gWt = G^T Z_Q,
+ *                     slot K of gbt = sum_rows G.
+ *   adapt_backward:   one workgroup per episode, for t = K-1 .. 0: U = Z_S gW_{t+1}^T + gb_{t+1}, R_t = P_t * (U - rowsum(P_t * U)),
+ *                     gW_t = gW_{t+1} - (a / S) R_t^T Z_S, gb_t = gb_{t+1} - (a / S) sum_rows R_t; then a launch behind it: the
+ *                     support rows of dfeats = -(a / S) sum_t ((P_t - Y) gW_{t+1} + R_t W_t) (t descending), dW0 [n_way, D] and
+ *                     db0 [n_way] = slot 0 of gWt / gbt summed over the episodes in order.
+ * Storage fp32, sums in double inside the kernels, fixed summation order, no atomics, every output element written once.
+ * MFT_EINVAL outside n_way 1..32, S 1..256, n_support / n_query / episodes >= 1, D = 512, inner_steps 1..16, inner_lr > 0,
+ * ld >= D a multiple of 4 (ldd >= D), 16-byte aligned feats / W0 / Wt / gWt / dfeats / dW0, or a null pointer (P of adapt excepted). */
+int mft_anil_adapt(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* W0,
+                   const float* b0, int inner_steps, float inner_lr, float* Wt, float* bt, float* P, void* stream);
+int mft_anil_scores(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int inner_steps,
+                    const float* Wt, const float* bt, float* scores, void* stream);
+int mft_anil_scores_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int inner_steps,
+                             const float* Wt, const float* dscores, float* dfeats, int ldd, float* gWt, float* gbt, void* stream);
+int mft_anil_adapt_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, int inner_steps,
+                            float inner_lr, const float* Wt, const float* P, float* gWt, float* gbt, float* R, float* dfeats, int ldd,
+                            float* dW0, float* db0, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

@@ -805,6 +805,44 @@ def dkt_scores(feats, mean, raw_outputscale, raw_noise, n_way, n_support, n_quer
     return ops.dkt_scores(feats.detach(), tuple(p.detach() for p in hyper), episodes, n_way, n_support, n_query, kernel=kernel)
 
 
+class _AnilHeadFn(torch.autograd.Function):
+    """ANIL head with a hand-written second-order backward: ops.anil_forward keeps the classifier and the
+    softmax of every inner step, ops.anil_backward returns the gradients of every feature row (support rows through the inner
+    steps, query rows through the scores) and of the classifier's initialisation."""
+
+    @staticmethod
+    def forward(ctx, feats, W0, b0, n_way, n_support, n_query, episodes, inner_steps, inner_lr):
+        scores, tape = ops.anil_forward(feats, W0.detach(), b0.detach(), episodes, n_way, n_support, n_query, inner_steps, inner_lr,
+                                        save=True)
+        ctx.save_for_backward(feats)
+        ctx.tape = {k: v for k, v in tape.items() if k != "feats"}
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.is_contiguous()) else dscores.contiguous().float()
+        dfeats, dW0, db0 = ops.anil_backward(dict(ctx.tape, feats=feats), d)
+        need = ctx.needs_input_grad
+        return (dfeats if need[0] else None, dW0 if need[1] else None, db0 if need[2] else None, None, None, None, None, None, None)
+
+
+def anil_scores(feats, W0, b0, n_way, n_support, n_query, episodes=1, inner_steps=5, inner_lr=0.01):
+    """ANIL.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode
+    after the other), the classifier's initialisation W0 [n_way, 512], b0 [n_way] -> scores [episodes*n_way*n_query, n_way] of the
+    classifier after ``inner_steps`` gradient steps of size ``inner_lr`` on the episode's support rows.  Differentiable (features
+    and initialisation, exactly, through the inner steps) when autograd records; the no-grad path saves nothing."""
+    _require_cuda(feats, "ANIL head")
+    _require_cuda(W0, "ANIL head")
+    _require_cuda(b0, "ANIL head")
+    ops.anil_check(episodes, n_way, n_support, n_query, inner_steps, inner_lr, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and (feats.requires_grad or W0.requires_grad or b0.requires_grad):
+        return _AnilHeadFn.apply(feats, W0, b0, n_way, n_support, n_query, episodes, inner_steps, inner_lr)
+    return ops.anil_forward(feats.detach(), W0.detach(), b0.detach(), episodes, n_way, n_support, n_query, inner_steps, inner_lr)[0]
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

@@ -1721,6 +1721,98 @@ def dkt_scores(feats, hyper, episodes, n_way, n_support, n_query, kernel="cossim
     return scores
 
 
+# ---------------------------------------------------------------------------------------------- ANIL head (csrc/anil.hip)
+ANIL_D, ANIL_MAX_WAY, ANIL_MAX_S, ANIL_MAX_STEPS = 512, 32, 256, 16
+ANIL_MAX_EPISODES, ANIL_MAX_ROWS = 65535, (1 << 31) // ANIL_D   # per call: a grid dimension, and 32-bit element offsets of the rows
+ANIL_FORWARD_LAUNCHES, ANIL_BACKWARD_LAUNCHES = 2, 3        # device kernels, at every shape
+
+
+def anil_check(episodes, n_way, n_support, n_query, inner_steps, inner_lr, D=ANIL_D):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != ANIL_D:
+        raise ValueError("ANIL head: feature dimension %d is not supported (D = %d)" % (D, ANIL_D))
+    if not 1 <= int(n_way) <= ANIL_MAX_WAY:
+        raise ValueError("ANIL head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), ANIL_MAX_WAY))
+    if int(n_support) < 1 or int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("ANIL head: n_support = %d, n_query = %d, episodes = %d (all must be >= 1)"
+                         % (int(n_support), int(n_query), int(episodes)))
+    if int(n_way) * int(n_support) > ANIL_MAX_S:
+        raise ValueError("ANIL head: S = n_way * n_support = %d is not supported (S <= %d: one workgroup walks the inner steps of an "
+                         "episode with its softmax panel in LDS)" % (int(n_way) * int(n_support), ANIL_MAX_S))
+    rows = int(episodes) * int(n_way) * (int(n_support) + int(n_query))
+    if int(episodes) > ANIL_MAX_EPISODES or rows >= ANIL_MAX_ROWS:
+        raise ValueError("ANIL head: episodes = %d, %d feature rows in all are not supported (episodes <= %d, rows < %d per call)"
+                         % (int(episodes), rows, ANIL_MAX_EPISODES, ANIL_MAX_ROWS))
+    if int(inner_steps) != inner_steps or not 1 <= int(inner_steps) <= ANIL_MAX_STEPS:
+        raise ValueError("ANIL head: inner_steps = %r is not supported (1 <= inner_steps <= %d)" % (inner_steps, ANIL_MAX_STEPS))
+    if not 0.0 < float(inner_lr) < float("inf"):
+        raise ValueError("ANIL head: inner_lr = %r (must be positive and finite)" % (inner_lr,))
+
+
+def _anil_rows(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("ANIL head: %s is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % (what, t.device))
+    if t.dtype != torch.float32:
+        raise RuntimeError("ANIL head: expected float32 %s, got %s" % (what, t.dtype))
+
+
+def anil_forward(feats, W0, b0, episodes, n_way, n_support, n_query, inner_steps, inner_lr, save=False):
+    """ANIL head: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode after the
+    other, row stride >= 512), W0 [n_way, 512], b0 [n_way] -> (scores [episodes*n_way*n_query, n_way], tape | None).  Two launches
+    whatever the shape: the walk of the ``inner_steps`` gradient steps of size ``inner_lr`` on each episode's support rows (one
+    workgroup per episode), the scores of the adapted classifier.  ``save``: keep the classifiers and softmaxes of every step for
+    anil_backward."""
+    _anil_rows(feats, "feats")
+    _anil_rows(W0, "W0")
+    _anil_rows(b0, "b0")
+    if feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("ANIL head: expected rows [R, D] with unit column stride, got %s" % (tuple(feats.shape),))
+    anil_check(episodes, n_way, n_support, n_query, inner_steps, inner_lr, feats.shape[1])
+    E, D, K = int(episodes), ANIL_D, int(inner_steps)
+    N, S, Q = n_way * (n_support + n_query), n_way * n_support, n_way * n_query
+    if feats.shape[0] != E * N:
+        raise ValueError("ANIL head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]" % (tuple(feats.shape), E * N, D))
+    if feats.stride(0) < D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("ANIL head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), D))
+    if tuple(W0.shape) != (n_way, D) or tuple(b0.shape) != (n_way,):
+        raise ValueError("ANIL head: W0 %s, b0 %s are not [%d, %d], [%d]" % (tuple(W0.shape), tuple(b0.shape), n_way, D, n_way))
+    if not W0.is_contiguous() or not b0.is_contiguous() or W0.data_ptr() % 16 != 0:
+        raise ValueError("ANIL head: W0 and b0 must be contiguous, W0 16-byte aligned")
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    Wt, bt, scores = new(E, K + 1, n_way, D), new(E, K + 1, n_way), new(E * Q, n_way)
+    P = new(E, K, S, n_way) if save else None
+    lr = float(inner_lr)
+    _lib.call("mft_anil_adapt", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, _p(W0), _p(b0), K, lr, _p(Wt), _p(bt), _p(P),
+              _stream())
+    _lib.call("mft_anil_scores", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, K, _p(Wt), _p(bt), _p(scores), _stream())
+    if not save:
+        return scores, None
+    return scores, dict(feats=feats, W=Wt, b=bt, P=P, shape=(E, n_way, n_support, n_query), inner_steps=K, inner_lr=lr)
+
+
+def anil_backward(tape, dscores):
+    """(dfeats [rows, 512] with every row written, dW0 [n_way, 512], db0 [n_way]) from the forward's tape and ``dscores``
+    [episodes*n_way*n_query, n_way] (float32, read on the device).  Three device kernels whatever the shape: the query side (dZ_Q and
+    each episode's gW, gb behind the last step), the reverse walk with the softmax Jacobian (one workgroup per episode), and behind
+    it dZ_S from the tapes with the sum of the episodes' gradients in episode order."""
+    E, n_way, n_support, n_query = tape["shape"]
+    K, lr, feats = tape["inner_steps"], tape["inner_lr"], tape["feats"]
+    D, N, S, Q = ANIL_D, n_way * (n_support + n_query), n_way * n_support, n_way * n_query
+    _anil_rows(dscores, "d(scores)")
+    if tuple(dscores.shape) != (E * Q, n_way) or not dscores.is_contiguous():
+        raise ValueError("ANIL head: d(scores) %s is not a contiguous [%d, %d]" % (tuple(dscores.shape), E * Q, n_way))
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    gW, gb, R = new(E, K + 1, n_way, D), new(E, K + 1, n_way), new(E, K, S, n_way)
+    dfeats, dW0, db0 = new(E * N, D), new(n_way, D), new(n_way)
+    _lib.call("mft_anil_scores_backward", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, K, _p(tape["W"]), _p(dscores),
+              _p(dfeats), D, _p(gW), _p(gb), _stream())
+    _lib.call("mft_anil_adapt_backward", _p(feats), feats.stride(0), E, n_way, n_support, n_query, D, K, lr, _p(tape["W"]), _p(tape["P"]),
+              _p(gW), _p(gb), _p(R), _p(dfeats), D, _p(dW0), _p(db0), _stream())
+    return dfeats, dW0, db0
+
+
 # ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
 SVM_C = 0.1                        # the published C_reg; a constant of the kernels
 SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1

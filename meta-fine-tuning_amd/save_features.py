@@ -15,7 +15,7 @@ from .data.feature_loader import save_features_file
 from .io_utils import get_assigned_file, get_best_file, get_resume_file, method_dir_name, model_dict, parse_args
 
 BASELINES = ('baseline', 'baseline++')
-METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt')
+METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil')
 SPLIT_SEEDS = {'base': 0, 'val': 2, 'novel': 3}       # miniImageNet-shaped pool per --split; 'base' is train.main's pool (seed 0)
 TEST_DATASET_SEED = 1                                 # --test_dataset X: the pool finetune.main evaluates on
 CHUNK = 200                                           # images per backbone forward
@@ -63,7 +63,8 @@ def resolve_state(p, verbose=True):
         # the stand-in is a GnnNet state: keep its backbone, put the method's own seeded head behind it
         state = type(state)((k, v) for k, v in state.items() if k.startswith("feature."))
         state.update({'matchingnet': synthetic.matchingnet_head_state, 'metaoptnet': synthetic.metaoptnet_head_state,
-                      'tpn': synthetic.tpn_head_state, 'feat': synthetic.feat_head_state, 'dkt': synthetic.dkt_head_state}.get(p.method, dict)())
+                      'tpn': synthetic.tpn_head_state, 'feat': synthetic.feat_head_state, 'dkt': synthetic.dkt_head_state,
+                      'anil': lambda: synthetic.anil_head_state(n_way=p.test_n_way)}.get(p.method, dict)())
     return state, loaded
 
 

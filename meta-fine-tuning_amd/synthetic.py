@@ -185,6 +185,17 @@ def dkt_head_state(seed=32):
     return sd
 
 
+def anil_head_state(seed=33, n_way=5, dim=512):
+    """The ANIL classifier's initialisation, state-dict keys and order of methods.anil.ANIL after ``feature.*``:
+    ``classifier.weight`` [n_way, dim] uniform in +-1/sqrt(dim) (the range of torch's default draw), ``classifier.bias`` ~ 0.1 N(0,1)
+    (off the constructor's zero so that a stand-in run exercises it)."""
+    rs = np.random.RandomState(seed)
+    sd = OrderedDict()
+    sd["classifier.weight"] = torch.from_numpy(rs.uniform(-1.0, 1.0, (n_way, dim)).astype(np.float32) / np.float32(np.sqrt(dim)))
+    sd["classifier.bias"] = torch.from_numpy((0.1 * rs.standard_normal(n_way)).astype(np.float32))
+    return sd
+
+
 FEAT_HEAD_KEYS = ("slf_attn.w_qs.weight", "slf_attn.w_ks.weight", "slf_attn.w_vs.weight", "slf_attn.layer_norm.weight",
                   "slf_attn.layer_norm.bias", "slf_attn.fc.weight", "slf_attn.fc.bias")
 
