@@ -731,6 +731,36 @@ int mft_anil_adapt_backward(const float* feats, int ld, int episodes, int n_way,
                             float inner_lr, const float* Wt, const float* P, float* gWt, float* gbt, float* R, float* dfeats, int ldd,
                             float* dW0, float* db0, void* stream);
 
+/* Mahalanobis head (csrc/mahalanobis.hip): scores[q, c] = -1/2 (z_q - mu_c)^T Q_c^-1 (z_q - mu_c) with the
+ * per-class regularised covariance Q_c = lambda S_c + (1 - lambda) S_t + beta I (lambda = n_support / (n_support + 1), beta = 1) of
+ * Simple CNAPS, and its exact backward; every episode of a step per launch.  feats as for the ridge head (D = 512, row stride ld),
+ * S = n_way * n_support support rows and Q = n_way * n_query query rows per episode.  T [episodes, S, D] = Z_S - mu_t,
+ * Mu [episodes, n_way, D] = the class means, G [episodes, S, S] (float64, lower triangle) = T T^T, W [episodes, Q, n_way, S] = the
+ * solutions w = K_c^-1 T (z_q - mu_c) of K_c = beta M_c^-1 + G; Om [episodes, Q, S], Ph [episodes, n_way, S], Ps [episodes, S, S]
+ * (float64) and X [episodes, S + n_way, D] are work arrays of the backward.
+ *   centre:   Mu and T.
+ *   gram:     G.
+ *   scores:   one workgroup per (episode, class): K_c packed in LDS, its Cholesky factor, then per query u = T d, the two solves and
+ *             scores [episodes * Q, n_way] = -(|d|^2 - u . w) / (2 beta).  W is nullable (not saved).
+ *   coef:     with g = dscores (DEVICE memory): Om[q, i] = sum_c g[q, c] w_qc[i], Ph[c, i] = sum_q g[q, c] w_qc[i],
+ *             Ps[i, j] = sum_{q, c} g[q, c] w_qc[i] w_qc[j].
+ *   backward: two launches: the query rows of dfeats (row stride ldd >= D) = (-sum_c g[q, c] z_q + g Mu + Om T) / beta and
+ *             X = [(Om^T Z_Q - Ph^T Mu - Ps T) / beta; (g^T Z_Q - diag(sum_q g) Mu - Ph T) / beta]; then the support rows of dfeats:
+ *             row i of class c = X[S + c] / n_support + X[i] - the column mean of X[0 .. S).
+ * Storage fp32 but for the float64 work arrays, sums in double inside the kernels, fixed summation order, no atomics, every output
+ * element written once.  MFT_EINVAL outside n_way 1..32, S 1..256, n_support / n_query >= 1, episodes 1..65535, fewer than 2^22 feature
+ * rows, D = 512, ld and ldd >= D multiples of 4, 16-byte aligned feats / T / Mu / X / dfeats, or a null pointer (W of scores excepted). */
+int mft_mahalanobis_centre(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, float* T, float* Mu,
+                           void* stream);
+int mft_mahalanobis_gram(int episodes, int n_way, int n_support, int n_query, int D, const float* T, double* G, void* stream);
+int mft_mahalanobis_scores(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* T,
+                           const float* Mu, const double* G, float* scores, float* W, void* stream);
+int mft_mahalanobis_coef(int episodes, int n_way, int n_support, int n_query, int D, const float* W, const float* dscores, double* Om,
+                         double* Ph, double* Ps, void* stream);
+int mft_mahalanobis_backward(const float* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D, const float* T,
+                             const float* Mu, const float* dscores, const double* Om, const double* Ph, const double* Ps, float* X,
+                             float* dfeats, int ldd, void* stream);
+
 /* Baseline++ head (backbone.distLinear: cosine classifier, class-wise learnable norm).  x rows of D floats (row stride ldx),
  * V [n_groups, C, D] and g [n_groups, C] contiguous.  With n_r = ||x_r||, xh_r = x_r / (n_r + 1e-5):
  *   scores[r, c] = s * g_c * (xh_r . v_c) / ||v_c||        (no bias; the caller passes s = 2 for C <= 200, else 10)

@@ -843,6 +843,39 @@ def anil_scores(feats, W0, b0, n_way, n_support, n_query, episodes=1, inner_step
     return ops.anil_forward(feats.detach(), W0.detach(), b0.detach(), episodes, n_way, n_support, n_query, inner_steps, inner_lr)[0]
 
 
+class _MahalanobisHeadFn(torch.autograd.Function):
+    """Mahalanobis head with a hand-written backward: ops.mahalanobis_forward keeps the class means, the
+    centred support rows and the solution w of every (query, class) pair, ops.mahalanobis_backward returns the gradient of every
+    feature row (query rows through d, support rows through the class means, the task mean and T)."""
+
+    @staticmethod
+    def forward(ctx, feats, n_way, n_support, n_query, episodes):
+        scores, tape = ops.mahalanobis_forward(feats, episodes, n_way, n_support, n_query, save=True)
+        ctx.save_for_backward(feats)
+        ctx.tape = {k: v for k, v in tape.items() if k != "feats"}
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        feats, = ctx.saved_tensors
+        d = dscores if (dscores.dtype == torch.float32 and dscores.is_contiguous()) else dscores.contiguous().float()
+        return ops.mahalanobis_backward(dict(ctx.tape, feats=feats), d), None, None, None, None
+
+
+def mahalanobis_scores(feats, n_way, n_support, n_query, episodes=1):
+    """Mahalanobis.set_forward tail: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one
+    episode after the other) -> scores [episodes*n_way*n_query, n_way] = minus half the squared Mahalanobis distance of every query
+    to every class mean under the class's regularised covariance.  Differentiable (support and query features, exactly) when
+    autograd records; the no-grad path saves nothing."""
+    _require_cuda(feats, "Mahalanobis head")
+    ops.mahalanobis_check(episodes, n_way, n_support, n_query, feats.shape[-1])
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    if torch.is_grad_enabled() and feats.requires_grad:
+        return _MahalanobisHeadFn.apply(feats, n_way, n_support, n_query, episodes)
+    return ops.mahalanobis_forward(feats.detach(), episodes, n_way, n_support, n_query)[0]
+
+
 class _NLLFn(torch.autograd.Function):
     """nn.NLLLoss()(logp, y) = -mean_r logp[r, y_r], one launch each way (mft_nll_mean / _backward)."""
 

@@ -33,13 +33,6 @@ static_assert(RIDGE_THREADS / 64 == 4, "dkt_grad_kernel and dkt_hyper_kernel add
 __device__ __forceinline__ double softplus_d(double x) { return (x > 0.0 ? x : 0.0) + log1p(exp(-fabs(x))); }
 __device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
 
-__device__ __forceinline__ void factor_by_size(float* __restrict__ sl, int M, int tid, double* __restrict__ sdiag) {
-    // 1024 threads over M rows: 4 threads per row up to 256 rows, 8 up to 128, 16 up to 64 (a function of the shape alone)
-    if (M > 128) cholesky_packed<4>(sl, M, tid, sdiag);
-    else if (M > 64) cholesky_packed<8>(sl, M, tid, sdiag);
-    else cholesky_packed<16>(sl, M, tid, sdiag);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- normalise
 // one wave per feats row: nrm = |z|, u = z / max(nrm, 1e-12) or z / sqrt(D)
 __global__ __launch_bounds__(RIDGE_THREADS) void dkt_normalise_kernel(const float* __restrict__ feats, int ld, long long rows, int linear,

@@ -1,6 +1,6 @@
 // Episode layout, domain and small device helpers shared by the two MetaOptNet heads: csrc/ridge.hip and
 // csrc/svm.hip (section 17); the packed-triangle Cholesky factor and the two triangular solves also serve csrc/tpn.hip (section 18)
-// and csrc/dkt.hip (section 20).
+// csrc/dkt.hip (section 20) and csrc/mahalanobis.hip (section 22).
 #pragma once
 #include "mft_common.h"
 
@@ -152,6 +152,13 @@ __device__ __forceinline__ void cholesky_packed(float* __restrict__ sl, int N, i
         if (live && part == 0) sl[rowi + kc] = i == kc ? (float)*sdiag : (float)(v / *sdiag);
         __syncthreads();
     }
+}
+
+__device__ __forceinline__ void factor_by_size(float* __restrict__ sl, int M, int tid, double* __restrict__ sdiag) {
+    // 1024 threads over M rows: 4 threads per row up to 256 rows, 8 up to 128, 16 up to 64 (a function of the shape alone)
+    if (M > 128) cholesky_packed<4>(sl, M, tid, sdiag);
+    else if (M > 64) cholesky_packed<8>(sl, M, tid, sdiag);
+    else cholesky_packed<16>(sl, M, tid, sdiag);
 }
 
 inline bool ridge_shape_ok(const void* feats, int ld, int episodes, int n_way, int n_support, int n_query, int D) {

@@ -185,7 +185,8 @@ def build_model(method, model_func, n_way, n_support, head="ridge", kernel=None)
     """The model `test` scores with: BaselineFinetune for the two baselines, GnnNet, or the method's class of train.HEAD_METHODS
     (``head``: MetaOptNet's, --head; ``kernel``: DKT's, --kernel)."""
     from .io_utils import KERNELS, method_dir_name
-    from .train import ADAPTIVE_METHODS, EMBEDDING_METHODS, HEAD_METHODS, PROBABILISTIC_METHODS, TRANSDUCTIVE_METHODS, head_method
+    from .train import (ADAPTIVE_METHODS, EMBEDDING_METHODS, HEAD_METHODS, METRIC_METHODS, PROBABILISTIC_METHODS, TRANSDUCTIVE_METHODS,
+                        head_method)
     method_dir_name(method, head, kernel)                 # a head / kernel that is unknown or not this method's is a ValueError
     if method == 'baseline':
         return BaselineFinetune(model_func, n_way, n_support)
@@ -199,4 +200,4 @@ def build_model(method, model_func, n_way, n_support, head="ridge", kernel=None)
             kw = dict(kernel=KERNELS[0] if kernel is None else kernel)
         return head_method(method)(model_func, n_way=n_way, n_support=n_support, **kw)
     raise NotImplementedError("--method %s: 'baseline', 'baseline++', 'gnnnet', %s are on the HIP path"
-                              % (method, ", ".join(repr(m) for m in sorted(list(HEAD_METHODS) + list(TRANSDUCTIVE_METHODS) + list(EMBEDDING_METHODS) + list(PROBABILISTIC_METHODS) + list(ADAPTIVE_METHODS)))))
+                              % (method, ", ".join(repr(m) for m in sorted(list(HEAD_METHODS) + list(TRANSDUCTIVE_METHODS) + list(EMBEDDING_METHODS) + list(PROBABILISTIC_METHODS) + list(ADAPTIVE_METHODS) + list(METRIC_METHODS)))))

@@ -179,9 +179,13 @@ def refuse_feature_wise_model(model_name, who):
 def refuse_transductive(model=None, method=None, who="finetune"):
     """TPN (methods/tpn.py) scores the queries of an episode together on a graph over support AND query nodes; the test-time engine
     adapts on the support rows and scores each query on its own.  FEAT (methods/feat.py) adapts the prototypes to each other with a
-    trained set-to-set function, DKT (methods/dkt.py) conditions a Gaussian process on the support rows, and ANIL (methods/anil.py)
-    takes gradient steps from a trained classifier initialisation; the engine has no mode for any of them."""
-    from .train import ADAPTIVE_METHODS, EMBEDDING_METHODS, PROBABILISTIC_METHODS, TRANSDUCTIVE_METHODS
+    trained set-to-set function, DKT (methods/dkt.py) conditions a Gaussian process on the support rows, ANIL (methods/anil.py)
+    takes gradient steps from a trained classifier initialisation, and Mahalanobis (methods/mahalanobis.py) scores with a covariance
+    per class; the engine has no mode for any of them."""
+    from .train import ADAPTIVE_METHODS, EMBEDDING_METHODS, METRIC_METHODS, PROBABILISTIC_METHODS, TRANSDUCTIVE_METHODS
+    if method in METRIC_METHODS or isinstance(model, tuple(METRIC_METHODS.values())):
+        raise NotImplementedError("%s --method %s: the test-time engine has no per-class-covariance mode; score the method with `test` "
+                                  "(save_features, then test --method %s)" % ((who,) + 2 * (method or model.METHOD,)))
     if method in ADAPTIVE_METHODS or isinstance(model, tuple(ADAPTIVE_METHODS.values())):
         raise NotImplementedError("%s --method %s: the test-time engine has no trained-initialisation inner-loop mode; score the method "
                                   "with `test` (save_features, then test --method %s)" % ((who,) + 2 * (method or model.METHOD,)))

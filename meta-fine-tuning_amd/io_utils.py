@@ -37,7 +37,7 @@ _COMMON = [
     ("--test_dataset", dict(default="", help="test dataset")),
     ("--unsupervised", dict(default="", help="unsupervised dataset")),
     ("--model", dict(default="ResNet10", help="backbone architecture")),
-    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/feat/dkt/anil/gnnnet/all")),
+    ("--method", dict(default="baseline", help="baseline/baseline++/protonet/matchingnet/metaoptnet/tpn/feat/dkt/anil/mahalanobis/gnnnet/all")),
     ("--head", dict(default="ridge", help="--method metaoptnet: its head, ridge (ridge regression) or svm")),
     ("--kernel", dict(default="cossim", help="--method dkt: its kernel, cossim (cosine similarity) or linear")),
     ("--train_n_way", dict(default=5, type=int, help="class num to classify for training")),

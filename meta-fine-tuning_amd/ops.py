@@ -1813,6 +1813,90 @@ def anil_backward(tape, dscores):
     return dfeats, dW0, db0
 
 
+# ---------------------------------------------------------------------------------------------- Mahalanobis head (csrc/mahalanobis.hip)
+MAHALANOBIS_D, MAHALANOBIS_MAX_WAY, MAHALANOBIS_MAX_S = 512, 32, 256
+MAHALANOBIS_MAX_EPISODES, MAHALANOBIS_MAX_ROWS = 65535, (1 << 31) // MAHALANOBIS_D   # per call: a grid dimension, 32-bit row offsets
+MAHALANOBIS_BETA = 1.0                                              # the ridge on every class covariance; a constant of the kernels
+MAHALANOBIS_FORWARD_LAUNCHES, MAHALANOBIS_BACKWARD_LAUNCHES = 3, 3  # device kernels, at every shape
+
+
+def mahalanobis_check(episodes, n_way, n_support, n_query, D=MAHALANOBIS_D):
+    """The launchers' domain (they return MFT_EINVAL outside it): raise ValueError before anything is launched."""
+    if D != MAHALANOBIS_D:
+        raise ValueError("Mahalanobis head: feature dimension %d is not supported (D = %d)" % (D, MAHALANOBIS_D))
+    if not 1 <= int(n_way) <= MAHALANOBIS_MAX_WAY:
+        raise ValueError("Mahalanobis head: n_way = %d is not supported (1 <= n_way <= %d)" % (int(n_way), MAHALANOBIS_MAX_WAY))
+    if int(n_support) < 1 or int(n_query) < 1 or int(episodes) < 1:
+        raise ValueError("Mahalanobis head: n_support = %d, n_query = %d, episodes = %d (all must be >= 1)"
+                         % (int(n_support), int(n_query), int(episodes)))
+    if int(n_way) * int(n_support) > MAHALANOBIS_MAX_S:
+        raise ValueError("Mahalanobis head: S = n_way * n_support = %d is not supported (S <= %d: one workgroup keeps the packed S x S "
+                         "factor of a class in LDS)" % (int(n_way) * int(n_support), MAHALANOBIS_MAX_S))
+    rows = int(episodes) * int(n_way) * (int(n_support) + int(n_query))
+    if int(episodes) > MAHALANOBIS_MAX_EPISODES or rows >= MAHALANOBIS_MAX_ROWS:
+        raise ValueError("Mahalanobis head: episodes = %d, %d feature rows in all are not supported (episodes <= %d, rows < %d per call)"
+                         % (int(episodes), rows, MAHALANOBIS_MAX_EPISODES, MAHALANOBIS_MAX_ROWS))
+
+
+def _mahalanobis_rows(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("Mahalanobis head: %s is on %s -- the MI355X path has no CPU fallback; call .cuda() first" % (what, t.device))
+    if t.dtype != torch.float32:
+        raise RuntimeError("Mahalanobis head: expected float32 %s, got %s" % (what, t.dtype))
+
+
+def mahalanobis_forward(feats, episodes, n_way, n_support, n_query, save=False):
+    """Mahalanobis head: feats [episodes*n_way*(n_support+n_query), 512] (class-major rows, one episode after
+    the other, row stride >= 512) -> (scores [episodes*n_way*n_query, n_way], tape | None).  Three launches whatever the shape: the
+    class means and the centred support rows, their Gram matrix, and the factor-and-solve launch (one workgroup per episode and
+    class).  ``save``: keep the solutions w of every (query, class) pair for mahalanobis_backward."""
+    _mahalanobis_rows(feats, "feats")
+    if feats.dim() != 2 or feats.stride(1) != 1:
+        raise RuntimeError("Mahalanobis head: expected rows [R, D] with unit column stride, got %s" % (tuple(feats.shape),))
+    mahalanobis_check(episodes, n_way, n_support, n_query, feats.shape[1])
+    E, D = int(episodes), MAHALANOBIS_D
+    N, S, Q = n_way * (n_support + n_query), n_way * n_support, n_way * n_query
+    if feats.shape[0] != E * N:
+        raise ValueError("Mahalanobis head: feats %s is not [episodes*n_way*(n_support+n_query) = %d, %d]" % (tuple(feats.shape), E * N, D))
+    if feats.stride(0) < D or feats.stride(0) % 4 != 0 or feats.data_ptr() % 16 != 0:
+        raise ValueError("Mahalanobis head: row stride %d (must be >= %d and a multiple of 4, rows 16-byte aligned)" % (feats.stride(0), D))
+    dev = feats.device
+    new = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
+    T, Mu, scores = new(E, S, D), new(E, n_way, D), new(E * Q, n_way)
+    G = torch.empty((E, S, S), device=dev, dtype=torch.float64)
+    W = new(E, Q, n_way, S) if save else None
+    shape = (E, n_way, n_support, n_query, D)
+    _lib.call("mft_mahalanobis_centre", _p(feats), feats.stride(0), *shape, _p(T), _p(Mu), _stream())
+    _lib.call("mft_mahalanobis_gram", *shape, _p(T), _p(G), _stream())
+    _lib.call("mft_mahalanobis_scores", _p(feats), feats.stride(0), *shape, _p(T), _p(Mu), _p(G), _p(scores), _p(W), _stream())
+    if not save:
+        return scores, None
+    return scores, dict(feats=feats, T=T, Mu=Mu, W=W, shape=(E, n_way, n_support, n_query))
+
+
+def mahalanobis_backward(tape, dscores):
+    """dfeats [rows, 512] (every row written) from the forward's tape and ``dscores`` [episodes*n_way*n_query, n_way] (float32, read
+    on the device).  Three device kernels whatever the shape: the coefficient matrices of the gradient rows from dscores and w, the
+    gradient rows as combinations of the rows of Z_Q, Mu and T (dZ_Q, and dT and the class-mean terms into a work array), and the
+    support rows from that array with the two mean corrections."""
+    E, n_way, n_support, n_query = tape["shape"]
+    feats = tape["feats"]
+    D, N, S, Q = MAHALANOBIS_D, n_way * (n_support + n_query), n_way * n_support, n_way * n_query
+    _mahalanobis_rows(dscores, "d(scores)")
+    if tuple(dscores.shape) != (E * Q, n_way) or not dscores.is_contiguous():
+        raise ValueError("Mahalanobis head: d(scores) %s is not a contiguous [%d, %d]" % (tuple(dscores.shape), E * Q, n_way))
+    dev = feats.device
+    new64 = lambda *s: torch.empty(s, device=dev, dtype=torch.float64)  # noqa: E731
+    Om, Ph, Ps = new64(E, Q, S), new64(E, n_way, S), new64(E, S, S)
+    X = torch.empty((E, S + n_way, D), device=dev, dtype=torch.float32)
+    dfeats = torch.empty((E * N, D), device=dev, dtype=torch.float32)
+    shape = (E, n_way, n_support, n_query, D)
+    _lib.call("mft_mahalanobis_coef", *shape, _p(tape["W"]), _p(dscores), _p(Om), _p(Ph), _p(Ps), _stream())
+    _lib.call("mft_mahalanobis_backward", _p(feats), feats.stride(0), *shape, _p(tape["T"]), _p(tape["Mu"]), _p(dscores), _p(Om), _p(Ph),
+              _p(Ps), _p(X), _p(dfeats), D, _stream())
+    return dfeats
+
+
 # ---------------------------------------------------------------------------------------------- MetaOptNet SVM head (csrc/svm.hip)
 SVM_C = 0.1                        # the published C_reg; a constant of the kernels
 SVM_MAX_PRODUCTS = 65536            # MFT_SVM_MAX_PRODUCTS: products M x [S, n_way] per episode before status = 1

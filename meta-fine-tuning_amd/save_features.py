@@ -15,7 +15,7 @@ from .data.feature_loader import save_features_file
 from .io_utils import get_assigned_file, get_best_file, get_resume_file, method_dir_name, model_dict, parse_args
 
 BASELINES = ('baseline', 'baseline++')
-METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil')
+METHODS = BASELINES + ('gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil', 'mahalanobis')
 SPLIT_SEEDS = {'base': 0, 'val': 2, 'novel': 3}       # miniImageNet-shaped pool per --split; 'base' is train.main's pool (seed 0)
 TEST_DATASET_SEED = 1                                 # --test_dataset X: the pool finetune.main evaluates on
 CHUNK = 200                                           # images per backbone forward

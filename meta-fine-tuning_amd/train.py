@@ -1,4 +1,4 @@
-"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / tpn / feat / dkt / anil / baseline / baseline++): Adam over all parameters, 100
+"""Meta-training driver (mirror of train.py:26-207 for --method gnnnet / protonet / matchingnet / metaoptnet / tpn / feat / dkt / anil / mahalanobis / baseline / baseline++): Adam over all parameters, 100
 episodes per epoch, checkpoints ``{'epoch','state'}`` under <save_dir>/checkpoints/<dataset>/<model>_<method>
 [_aug]_<n>way_<k>shot/<epoch>.tar, optional first-order-MAML meta-fine-tuning (--fine_tune).
 The episode source is the in-repo synthetic miniImageNet-shaped sampler (real data is out of scope)."""
@@ -12,6 +12,7 @@ from .io_utils import get_assigned_file, method_dir_name, model_dict, parse_args
 from .methods import gnnnet_copy
 from .methods.anil import ANIL
 from .methods.gnnnet import GnnNet
+from .methods.mahalanobis import Mahalanobis
 from .methods.matchingnet import MatchingNet
 from .methods.metaoptnet import MetaOptNet
 from .methods.protonet import ProtoNet
@@ -24,12 +25,13 @@ TRANSDUCTIVE_METHODS = {'tpn': TPN}     # HeadMethods that score an episode's qu
 EMBEDDING_METHODS = {'feat': FEAT}      # HeadMethods that adapt the embedding to the episode: trained and scored by `test`, no test-time engine mode
 PROBABILISTIC_METHODS = {'dkt': DKT}    # HeadMethods trained through a marginal likelihood instead of scores: scored by `test`, no test-time engine mode
 ADAPTIVE_METHODS = {'anil': ANIL}       # HeadMethods that adapt a classifier to the episode by gradient steps and train through them: scored by `test`, no test-time engine mode
+METRIC_METHODS = {'mahalanobis': Mahalanobis}     # HeadMethods that estimate a metric per class from the support rows: scored by `test`, no test-time engine mode
 
 
 def head_method(name):
-    """The HeadMethod class of ``--method name`` over the five tables, or None."""
+    """The HeadMethod class of ``--method name`` over the six tables, or None."""
     return (HEAD_METHODS.get(name) or TRANSDUCTIVE_METHODS.get(name) or EMBEDDING_METHODS.get(name) or PROBABILISTIC_METHODS.get(name)
-            or ADAPTIVE_METHODS.get(name))
+            or ADAPTIVE_METHODS.get(name) or METRIC_METHODS.get(name))
 
 
 class SyntheticEpisodeLoader:
@@ -240,8 +242,8 @@ def main(argv=None, n_episode=100, size=84, variant50=False, pool_images_per_cla
     rank, W = parallel.world()
     if not params.start_epoch > 0:
         np.random.seed(10)
-    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil'):
-        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil', 'baseline' and 'baseline++' are on the HIP path"
+    if params.method not in ('gnnnet', 'baseline', 'baseline++', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil', 'mahalanobis'):
+        raise NotImplementedError("--method %s: 'gnnnet', 'protonet', 'matchingnet', 'metaoptnet', 'tpn', 'feat', 'dkt', 'anil', 'mahalanobis', 'baseline' and 'baseline++' are on the HIP path"
                                   % params.method)
     if head_method(params.method) is not None and params.fine_tune:
         raise NotImplementedError("--method %s --fine_tune: %s's first-order-MAML meta-training is not on the HIP path"
